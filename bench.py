@@ -8,6 +8,12 @@ N > 1 ranks the records are gathered across ranks with RCCL (all_gather over xGM
 Frames shard across ranks (weak scaling: B frames per GPU).  Weights are seeded synthetic
 (real .pth files are unavailable offline).
 
+A plain run sets up, warms up, times --steps steps, writes the last timed step's outputs when
+--dump-outputs DIR is given, and prints the result line with the headline figure and the
+roofline of the timed region.  Everything that takes runs of its own (the profiled stage passes,
+the host-to-host pass, the Hand and single-frame latencies, the CPU baseline) runs only with
+--full and adds its keys to the same line.
+
 Prints ONE JSON line on rank 0 (driver contract) including:
 * roofline: the 7x7-conv kernel class (68 % of network FLOPs), algorithmic (fp32) FLOPs per
   launch / mean launch time from HIP events recorded around those launches (on the stream
@@ -15,10 +21,12 @@ Prints ONE JSON line on rank 0 (driver contract) including:
   of the step -- against the ceiling of the kernel that ran: the split-bf16 conv (default; six
   bf16 MFMA piece products per fp32 multiply-add -> bf16 peak / 6) or the fp32 MFMA conv
   (OPOSE_CONV=f32 -> fp32 MFMA peak);
-* stage_ms_per_step / stage_roofline: a separate profiled pass after the timed region;
 * steps overlap (OPOSE_PIPELINE): frames are resident and static, so step k+1's network runs
   on the library's second stream while step k's post-processing finishes (BENCH_PIPELINE=0:
   serial);
+and with --full:
+* stage_ms_per_step / stage_roofline: a separate profiled pass after the timed region;
+* value_host_to_host, c3_hand, latency_ms_single_frame: passes of their own after it;
 * cpu_baseline: the oracle (torch-CPU conv graph + NumPy/SciPy post-processing, proven
   identical to the reference on the golden fixtures) on a bounded sample of the same workload.
 """
@@ -57,6 +65,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32, help="frames per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled stage passes, the host-to-host pass, the "
+                         "Hand and single-frame latencies and the CPU baseline (the options below shape them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step to DIR as float64 .npy arrays")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="bounded CPU-baseline sample")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--latency-iters", type=int, default=10)
@@ -65,7 +78,10 @@ def parse():
                     help="steps of the host-to-host pass (pinned frames in, records out over PCIe); default --steps")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: gloo ranks gather synthetic host records (tests the launcher and the gather)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args):
@@ -428,6 +444,108 @@ def hand_c3(device, iters):
                                               for k, v in prof.items()})}
 
 
+def full_passes(args, body, frames, frames_np, rec, dev, rank, world, rate):
+    """--full: the measurements beside the headline `rate` (frames/s of the timed steps), each a
+    pass of its own after the timed region.  Returns their keys of the result line (rank 0)."""
+    # per-stage breakdown: separate profiled passes after the timed region, every launch
+    # bracketed by events.  The reported map comes from a serial pass (no step overlap): under
+    # the pipelined overlap the post-network kernels share the chip with the next network, which
+    # inflates both sides' own times; the pipelined pass is reported beside it.
+    prof_steps = max(2, min(args.steps, 5))
+
+    def profiled_pass(pipelined):
+        body.handle.profile(2 if args.detail else 1)
+        body.handle.profile_reset()
+        for _ in range(prof_steps):
+            body.infer_records(frames, rec, pipeline=pipelined)
+        body.handle.synchronize()
+        torch.cuda.synchronize()
+        p = body.handle.profile_read()
+        body.handle.profile(False)
+        return p
+
+    prof_pipe = profiled_pass(PIPELINE) if PIPELINE else None
+    prof = profiled_pass(False)
+    if args.detail and rank == 0:
+        det = sorted(((k, v) for k, v in prof.items() if k.startswith("layer/")), key=lambda kv: -kv[1]["ms"])
+        for k, v in det:
+            tf = v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] else 0
+            print(f"{k:70s} {v['ms'] / prof_steps:8.3f} ms/step {tf:7.1f} TF/s", file=sys.stderr)
+        prof = {k: v for k, v in prof.items() if not k.startswith("layer/")}
+        if prof_pipe:
+            prof_pipe = {k: v for k, v in prof_pipe.items() if not k.startswith("layer/")}
+    # host-to-host (PCIe-inclusive) pass: reported beside `value`, never as it
+    h2h_value, h2h_ms, h2h_info = host_to_host(body, frames_np, args.host_steps or args.steps, dev, rank, world)
+
+    c3 = hand_c3(dev.index, args.latency_iters) if rank == 0 and args.latency_iters > 0 else None
+
+    # single-frame latency (C2: one frame, host in -> host out through Body.__call__)
+    lat = []
+    if rank == 0 and args.latency_iters > 0:
+        one = frames_np[0]
+        body(one)
+        for _ in range(args.latency_iters):
+            t1 = time.perf_counter()
+            body(one)
+            lat.append(time.perf_counter() - t1)
+
+    if rank != 0:
+        return {}
+    conv_all = {k: v for k, v in prof.items() if k.startswith("conv")}
+    stage_ms = {k: round(v["ms"] / prof_steps, 4) for k, v in sorted(prof.items())}
+    net_flops = sum(v["flops"] for v in conv_all.values())
+    net_ms = sum(v["ms"] for v in conv_all.values())
+    out = {
+        "value_host_to_host": h2h_value,
+        "value_host_to_host_ratio": h2h_value / rate,
+        "host_to_host": dict(h2h_info, ms_per_step=h2h_ms, basis=(
+            "pinned host frames uploaded each step on per-buffer copy streams once the previous "
+            "network has read the buffer (opose_signal_input), records (and the RCCL gather when "
+            "n_gpus > 1) downloaded to pinned host memory each step on a stream of their own; "
+            "reference boundary src/body.py:44-50")),
+        "network_tflops": net_flops / (net_ms * 1e-3) / 1e12 if net_ms > 0 else 0.0,
+        "stage_breakdown": f"separate profiled passes of {prof_steps} steps after the timed region (events "
+                           "around every launch): stage_ms_per_step / stage_roofline from a serial pass (no "
+                           "step overlap), *_pipelined from a pass with the bench's overlap; the timed region "
+                           "brackets only the 7x7 convs",
+        "stage_ms_per_step": stage_ms,
+        "stage_roofline": stage_roofline(prof),
+        "stage_ms_per_step_pipelined": ({k: round(v["ms"] / prof_steps, 4) for k, v in sorted(prof_pipe.items())}
+                                        if prof_pipe else None),
+        "stage_roofline_pipelined": stage_roofline(prof_pipe) if prof_pipe else None,
+        "latency_ms_single_frame": (float(np.median(lat)) * 1e3) if lat else None,
+        "c3_hand": c3,
+    }
+    if not args.no_cpu and world == 1:
+        out["cpu_baseline"] = cpu_baseline(frames_np[:8], args.cpu_seconds)
+    return out
+
+
+DUMP_LIMIT = 64 << 20  # bytes a dump may hold in all
+
+
+def dump_outputs(path, records, ppp, maxp):
+    """The last timed step's records ([n_frames, record_bytes] uint8 on the host) as the arrays a
+    caller decodes from them (src/_native.py decode_record), stacked over frames in float64:
+    counts.npy [n, 3] (status, keypoints, people), candidate.npy [n, 18 * ppp, 4] and subset.npy
+    [n, maxp, 20].  Rows past a frame's counts are no output (decode_record drops them): zeroed.
+    Frames are seeded, so two builds run with the same arguments are compared array for array;
+    past DUMP_LIMIT only the first frames are kept."""
+    cap_c = 18 * ppp
+    per_frame = 8 * (3 + 4 * cap_c + 20 * maxp)
+    n = min(len(records), max(1, (DUMP_LIMIT - 3 * 256) // per_frame))  # 256: above an .npy header
+    recs = records[:n]
+    counts = recs[:, :12].copy().view(np.int32).astype(np.float64)
+    cand = recs[:, 16:16 + 32 * cap_c].copy().view(np.float64).reshape(n, cap_c, 4)
+    off = 16 + 32 * cap_c
+    sub = recs[:, off:off + 160 * maxp].copy().view(np.float64).reshape(n, maxp, 20)
+    cand[np.arange(cap_c)[None, :] >= counts[:, 1, None]] = 0
+    sub[np.arange(maxp)[None, :] >= counts[:, 2, None]] = 0
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("counts", counts), ("candidate", cand), ("subset", sub)):
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -478,7 +596,8 @@ def main():
             # RCCL all_gather of the per-frame keypoint records, ordered after the library's
             # kernels on its stream (src/dist.py)
             with torch.cuda.stream(lib_stream):
-                gather_records(rec, world * B, world)
+                return gather_records(rec, world * B, world)
+        return rec
 
     for _ in range(args.warmup):
         step()
@@ -498,13 +617,13 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     if DEFER and world > 1:
         # each step gathered the records complete at that point (the previous step's, deferred):
         # the last step's post-processing is flushed and gathered here
         body.handle.flush()
         with torch.cuda.stream(lib_stream):
-            gather_records(rec, world * B, world)
+            last = gather_records(rec, world * B, world)
     body.handle.synchronize()
     torch.cuda.synchronize()
     if world > 1:
@@ -514,56 +633,15 @@ def main():
     body.handle.profile(False)
     if world > 1:
         dt = max_over_ranks(dt, dev)
-    # per-stage breakdown: separate profiled passes after the timed region, every launch
-    # bracketed by events.  The reported map comes from a serial pass (no step overlap): under
-    # the pipelined overlap the post-network kernels share the chip with the next network, which
-    # inflates both sides' own times; the pipelined pass is reported beside it.
-    prof_steps = max(2, min(args.steps, 5))
-
-    def profiled_pass(pipelined):
-        body.handle.profile(2 if args.detail else 1)
-        body.handle.profile_reset()
-        for _ in range(prof_steps):
-            body.infer_records(frames, rec, pipeline=pipelined)
-        body.handle.synchronize()
-        torch.cuda.synchronize()
-        p = body.handle.profile_read()
-        body.handle.profile(False)
-        return p
-
-    prof_pipe = profiled_pass(PIPELINE) if PIPELINE else None
-    prof = profiled_pass(False)
-    if args.detail and rank == 0:
-        det = sorted(((k, v) for k, v in prof.items() if k.startswith("layer/")), key=lambda kv: -kv[1]["ms"])
-        for k, v in det:
-            tf = v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] else 0
-            print(f"{k:70s} {v['ms'] / prof_steps:8.3f} ms/step {tf:7.1f} TF/s", file=sys.stderr)
-        prof = {k: v for k, v in prof.items() if not k.startswith("layer/")}
-        if prof_pipe:
-            prof_pipe = {k: v for k, v in prof_pipe.items() if not k.startswith("layer/")}
-    # host-to-host (PCIe-inclusive) pass: reported beside `value`, never as it
-    h2h_value, h2h_ms, h2h_info = host_to_host(body, frames_np, args.host_steps or args.steps, dev, rank, world)
-
-    c3 = hand_c3(local, args.latency_iters) if rank == 0 and args.latency_iters > 0 else None
-
-    # single-frame latency (C2: one frame, host in -> host out through Body.__call__)
-    lat = []
-    if rank == 0 and args.latency_iters > 0:
-        one = frames_np[0]
-        body(one)
-        for _ in range(args.latency_iters):
-            t1 = time.perf_counter()
-            body(one)
-            lat.append(time.perf_counter() - t1)
+    frames_total = world * B * args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last.cpu().numpy(), body.peaks_per_part, body.max_people)
+    # every rank takes part in the passes of --full; rank 0 reports them
+    full = full_passes(args, body, frames, frames_np, rec, dev, rank, world, frames_total / dt) if args.full else {}
 
     if rank == 0:
-        frames_total = world * B * args.steps
         c7 = prof_timed.get("conv7x7", {"count": 0, "ms": 0.0, "flops": 0.0})
-        conv_all = {k: v for k, v in prof.items() if k.startswith("conv")}
         achieved = (c7["flops"] / (c7["ms"] * 1e-3) / 1e12) if c7["ms"] > 0 else 0.0
-        stage_ms = {k: round(v["ms"] / prof_steps, 4) for k, v in sorted(prof.items())}
-        net_flops = sum(v["flops"] for v in conv_all.values())
-        net_ms = sum(v["ms"] for v in conv_all.values())
         out = {
             "metric": "frames/sec (body+PAF grouping) at 368x656",
             "value": frames_total / dt,
@@ -588,13 +666,6 @@ def main():
                                        "network of step k+1 overlaps post-processing of step k (OPOSE_PIPELINE)"
                        if PIPELINE else "none"},
             "frames_total": frames_total,
-            "value_host_to_host": h2h_value,
-            "value_host_to_host_ratio": h2h_value / (frames_total / dt),
-            "host_to_host": dict(h2h_info, ms_per_step=h2h_ms, basis=(
-                "pinned host frames uploaded each step on per-buffer copy streams once the previous "
-                "network has read the buffer (opose_signal_input), records (and the RCCL gather when "
-                "n_gpus > 1) downloaded to pinned host memory each step on a stream of their own; "
-                "reference boundary src/body.py:44-50")),
             "roofline": {"bound": "mfma", "kernel": CONV_KERNEL + " (7x7 CPM stages)",
                          "achieved": achieved, "peak": PEAK_CONV_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved / PEAK_CONV_TFLOPS,
@@ -604,24 +675,12 @@ def main():
                          "mean_launch_ms": c7["ms"] / max(1, c7["count"]), "traffic": pmc_traffic(),
                          "traffic_unit": "bytes per launch (FETCH_SIZE*2 + WRITE_SIZE)*1KiB, profiles/pmc_summary.json",
                          "traffic_same_library": pmc_traffic_lib_match()},
-            "network_tflops": net_flops / (net_ms * 1e-3) / 1e12 if net_ms > 0 else 0.0,
-            "stage_breakdown": f"separate profiled passes of {prof_steps} steps after the timed region (events "
-                               "around every launch): stage_ms_per_step / stage_roofline from a serial pass (no "
-                               "step overlap), *_pipelined from a pass with the bench's overlap; the timed region "
-                               "brackets only the 7x7 convs",
-            "stage_ms_per_step": stage_ms,
-            "stage_roofline": stage_roofline(prof),
-            "stage_ms_per_step_pipelined": ({k: round(v["ms"] / prof_steps, 4) for k, v in sorted(prof_pipe.items())}
-                                            if prof_pipe else None),
-            "stage_roofline_pipelined": stage_roofline(prof_pipe) if prof_pipe else None,
-            "latency_ms_single_frame": (float(np.median(lat)) * 1e3) if lat else None,
-            "c3_hand": c3,
             "frames_status_nonzero": int((statuses != 0).sum()),
             "mean_peaks_per_frame": float(counts[:, 0].mean()),
             "mean_people_per_frame": float(counts[:, 1].mean()),
+            "full": args.full,
         }
-        if not args.no_cpu and world == 1:
-            out["cpu_baseline"] = cpu_baseline(frames_np[:8], args.cpu_seconds)
+        out.update(full)
         print(json.dumps(out))
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp PYTHONDONTWRITEBYTECODE=1
 OUT=gpurun_out/prof
 mkdir -p $OUT
-ARGS="bench.py --steps ${STEPS:-3} --warmup 1 --no-cpu --latency-iters 0 ${EXTRA:-}"
+ARGS="bench.py --full --steps ${STEPS:-3} --warmup 1 --no-cpu --latency-iters 0 ${EXTRA:-}"
 run() {  # name, rocprof args...
   local name=$1; shift
   timeout -k 10 300 rocprofv3 "$@" -d $OUT/$name -o $name --output-format csv -- python3 $ARGS > $OUT/$name.log 2>&1
