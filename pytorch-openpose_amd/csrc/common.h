@@ -88,11 +88,11 @@ struct X6Group {
     int N, H, W;           // this group's frames (stride-1 'same' conv; pooled: the input's H, W)
     int npix;              // GEMM columns: N*H*W (pooled: N*(H/2)*(W/2)*4, quad-major)
     int ylo, yhi;          // conv_x6 taps read rows [ylo, yhi) (yhi == 0: [0, H)); a row band's
-                           // view (engine.cpp Band) also reads its halo rows
+                           // view (engine.h Band) also reads its halo rows
     // k slabs: every tile of this group sums its nK chunks as `slabs` fixed ranges [s nK / slabs,
     // (s + 1) nK / slabs), each accumulated from zero, folded in slab order by conv_x6_fixup
     // (slabs == 1: one run over all chunks, written by the conv itself).  The count is a function
-    // of the layer and the segment's logical geometry only (engine.cpp slab_count), never of the
+    // of the layer and the segment's logical geometry only (engine_plan.cpp slab_count), never of the
     // launch's grid, groups or row band: a pixel sums in the same order whatever launch computes it.
     int slabs;
     int tpf;               // conv_wino_x6: tile slots per frame (frame-aligned blocks of 128), 0: tiles

@@ -14,7 +14,7 @@
 // and split into three bf16 pieces again, so every GEMM is the six-piece-product split-bf16
 // product of conv_x6 (fp32-class; tests/test_gpu_x6.py::test_wino_conv_fp32_accuracy).  The
 // output pair is anchored at even x of the frame, so a pixel's value does not depend on the
-// launch, the batch, the grid or a row band (engine.cpp seg_kernel).
+// launch, the batch, the grid or a row band (engine_plan.cpp seg_kernel).
 //
 // Workgroup: 128 output channels x 128 tiles (output pairs) = 256 output pixels, 4 waves (one
 // per SIMD, 512 registers each), wave w owns tiles [32 w, 32 w + 32) of all 128 channels:

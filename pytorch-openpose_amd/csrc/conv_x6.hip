@@ -622,7 +622,7 @@ void launch_x6p_clear_pads(uint8_t* const* bufs, const int* planes, int nbufs, i
                        N, H, W, P);
 }
 
-// Halo rows of a row band (engine.cpp band_halo): 3 consecutive rows of groups [g0, g0 + ng) of
+// Halo rows of a row band (engine_net.cpp band_halo): 3 consecutive rows of groups [g0, g0 + ng) of
 // each piece plane of a one-frame X6P buffer <-> a packed [piece][group][3 P] unit block.
 // blockIdx.y = direction d (0: the band's top edge, 1: its bottom edge), skipped unless bit d of
 // mask; row[d]: the padded row (3 + y) of the block's first row.

@@ -1,0 +1,766 @@
+// engine_api.cpp — the inference entry points of libopose and what drives them: input staging, the
+// launch-sequence (hipGraph) cache, the scales of a pyramid, cross-call pipelining.
+#include "engine.h"
+
+namespace opose {
+
+// bytes a strided uint8 [N][H][W][3] host view spans: the last row ends 3*W bytes after its start,
+// so a view cut from the bottom-right of a larger buffer is never read past its end
+static size_t host_span(int N, int H, int W, int64_t row_stride, int64_t frame_stride) {
+    return (size_t)(N - 1) * (size_t)frame_stride + (size_t)(H - 1) * (size_t)row_stride + (size_t)W * 3;
+}
+
+// a strided uint8 [N][H][W][3] view of the frames on the device: the caller's pointer
+// (OPOSE_IN_DEVICE), or the copy of the host frames in h->frames
+static const uint8_t* stage_frames(opose_ctx* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                                   int64_t frame_stride, int flags) {
+    if (flags & OPOSE_IN_DEVICE) return bgr;
+    uint8_t* buf = h->frames.ensure<uint8_t>((size_t)frame_stride * N, h->stream);
+    OPOSE_HIP_CHECK(hipMemcpyAsync(buf, bgr, host_span(N, H, W, row_stride, frame_stride), hipMemcpyHostToDevice,
+                                   h->stream));
+    return buf;
+}
+
+// n floats of network maps on the device: the caller's pointer (OPOSE_IN_DEVICE), or the copy of
+// the host maps in h->maps_in.  One buffer: a multi-scale entry point consumes a scale's maps on
+// the handle's stream before it stages the next scale's.
+static const float* stage_maps(opose_ctx* h, const float* maps, size_t n, int flags) {
+    if (flags & OPOSE_IN_DEVICE) return maps;
+    float* buf = h->maps_in.ensure<float>(n, h->stream);
+    OPOSE_HIP_CHECK(hipMemcpyAsync(buf, maps, n * 4, hipMemcpyHostToDevice, h->stream));
+    return buf;
+}
+
+// cv2.resize + pad + normalise of N frames into the network input x of scale g (imgproc.hip)
+void preprocess_scale(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
+                      const ScaleGeom& g, const opose_params& p, float* x, hipStream_t stream) {
+    launch_preprocess(frames, frame_stride, row_stride, N, H, W, g.Hs, g.Ws, 1.0 / g.mult, 1.0 / g.mult, g.Hp, g.Wp,
+                      (float)p.pad_value / 256.f - 0.5f, x, stream);
+}
+
+static opose_params fill_params(const opose_params* p, int net) {
+    opose_params q;
+    if (p) q = *p;
+    else opose_default_params(net, &q);
+    if (q.n_scales < 1 || q.n_scales > OPOSE_MAX_SCALES || q.stride != 8 || q.boxsize <= 0)
+        throw std::invalid_argument("bad opose_params");
+    return q;
+}
+
+// Run `work` (device work only: kernels, device memsets/copies on h->stream, no host sync,
+// no allocation once warm) through the launch-sequence cache keyed by `key`.  Captures stay on
+// the one stream (h->capturing: run_scales_concurrently runs its scales one after another), and
+// a captured graph that is not a single chain of nodes is refused (linear_graph).  Cause: in a
+// torch process the library runs on torch's bundled HIP runtime (libamdhip64 7.0.2, SONAME
+// libamdhip64.so.7, loaded before ours), whose hipGraphLaunch segfaults on a freshly instantiated
+// forked graph after other forked executables were destroyed.  scripts/graph_fork_repro.hip
+// reproduces it without libopose: the same program crashes under 7.0.2 and runs clean
+// under /opt/rocm's 7.2, with no fork in captures, or with no executable destroyed.
+// a chain: one root, nodes - 1 edges, and no node with more than one successor (a tree with
+// nodes - 1 edges and one root may still branch)
+static bool linear_graph(hipGraph_t g) {
+    size_t nodes = 0, edges = 0, roots = 0;
+    OPOSE_HIP_CHECK(hipGraphGetNodes(g, nullptr, &nodes));
+    OPOSE_HIP_CHECK(hipGraphGetEdges(g, nullptr, nullptr, &edges));
+    OPOSE_HIP_CHECK(hipGraphGetRootNodes(g, nullptr, &roots));
+    if (nodes == 0) return true;
+    if (roots != 1 || edges != nodes - 1) return false;
+    std::vector<hipGraphNode_t> all(nodes);
+    OPOSE_HIP_CHECK(hipGraphGetNodes(g, all.data(), &nodes));
+    for (hipGraphNode_t n : all) {
+        size_t succ = 0;
+        OPOSE_HIP_CHECK(hipGraphNodeGetDependentNodes(n, nullptr, &succ));
+        if (succ > 1) return false;
+    }
+    return true;
+}
+
+template <class F>
+static void run_graphed(opose_ctx* h, const std::string& key, F&& work) {
+    if (!h->use_graphs || h->prof || !h->stream) {
+        work();
+        return;
+    }
+    const uint64_t epoch = g_alloc_epoch.load();
+    auto it = h->graphs.find(key);
+    if (it != h->graphs.end() && it->second.eager) {  // refused once: never captured again
+        work();
+        return;
+    }
+    if (it != h->graphs.end() && it->second.exec && it->second.epoch == epoch) {
+        OPOSE_HIP_CHECK(hipGraphLaunch(it->second.exec, h->stream));
+        return;
+    }
+    if (it == h->graphs.end() || it->second.epoch != epoch) {  // first sighting: eager, allocates
+        if (it != h->graphs.end() && it->second.exec) OPOSE_HIP_CHECK(hipGraphExecDestroy(it->second.exec));
+        work();
+        h->graphs[key] = GraphEntry{nullptr, g_alloc_epoch.load()};
+        return;
+    }
+    // second sighting with nothing reallocated since: capture, instantiate, launch
+    OPOSE_HIP_CHECK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    try {
+        Redirect<bool> capturing(h->capturing, true);
+        work();
+    } catch (...) {
+        hipGraph_t g = nullptr;
+        (void)hipStreamEndCapture(h->stream, &g);
+        if (g) (void)hipGraphDestroy(g);
+        throw;
+    }
+    hipGraph_t g = nullptr;
+    OPOSE_HIP_CHECK(hipStreamEndCapture(h->stream, &g));
+    if (!linear_graph(g)) {
+        // a fork inside a capture (see above): never instantiated.  The captured work did not run,
+        // so run it eagerly now, and keep this signature eager (no capture on every later call)
+        (void)hipGraphDestroy(g);
+        it->second.eager = true;
+        work();
+        return;
+    }
+    if (g_alloc_epoch.load() != epoch) {  // something allocated inside the capture: not replayable
+        (void)hipGraphDestroy(g);
+        h->graphs.erase(key);
+        work();
+        return;
+    }
+    hipGraphExec_t ex = nullptr;
+    const hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    OPOSE_HIP_CHECK(e);
+    it->second.exec = ex;
+    OPOSE_HIP_CHECK(hipGraphLaunch(ex, h->stream));
+}
+
+static std::string call_key(const char* what, int N, int H, int W, int64_t rs, int64_t fs, const opose_params& p,
+                            const void* in_dev, const void* out_dev, int ppp, int maxp) {
+    std::string k(what);
+    char tmp[256];
+    std::snprintf(tmp, sizeof tmp, "|%d|%d|%d|%lld|%lld|%p|%p|%d|%d|", N, H, W, (long long)rs, (long long)fs, in_dev,
+                  out_dev, ppp, maxp);
+    k += tmp;
+    k.append(reinterpret_cast<const char*>(&p), sizeof p);
+    return k;
+}
+
+// the deferred post-network part (OPOSE_PIPELINE_DEFER) on the handle's stream, after `after`
+static void enqueue_deferred_post(opose_ctx* h, hipEvent_t after) {
+    opose_ctx::DeferredPost& d = h->dpost;
+    if (!d.pending) return;
+    d.pending = false;
+    OPOSE_HIP_CHECK(hipStreamWaitEvent(h->stream, after, 0));
+    {
+        Redirect<int> mid_set(h->mid_set, d.set);
+        body_post_common(h, d.N, d.H, d.W, d.gs, d.p, d.rec);
+    }
+    OPOSE_HIP_CHECK(hipEventRecord(h->ev_post[d.set], h->stream));
+    h->post_pending[d.set] = true;
+}
+
+// enqueue a deferred post-network part now (after its whole network)
+void flush_post(opose_ctx* h) {
+    if (h->dpost.pending) enqueue_deferred_post(h, h->ev_net);
+}
+
+// every entry point that enqueues work on the handle's stream (other than the pipelined body
+// path): select the device, and make the next pipelined network wait for that stream
+void enter_main(opose_ctx* h) {
+    OPOSE_HIP_CHECK(hipSetDevice(h->device));
+    flush_post(h);
+    h->main_dirty = true;
+}
+
+// fn(s) for every scale s, scale s on stream s (0: the handle's stream, others its scale
+// streams), each with workspace slot s; the handle's stream continues after all of them
+static void run_scales_concurrently(opose_ctx* h, int ns, const std::function<void(int)>& fn) {
+    Redirect<int> slot(h->slot);
+    if (h->capturing) {  // one stream while capturing (run_graphed): same work, same slots
+        for (int s = ns - 1; s >= 0; --s) {
+            h->slot = s;
+            fn(s);
+        }
+        return;
+    }
+    const hipStream_t main = h->stream;
+    if (!h->ev_fork) OPOSE_HIP_CHECK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    OPOSE_HIP_CHECK(hipEventRecord(h->ev_fork, main));
+    for (int s = 1; s < ns; ++s) {
+        if (!h->sstream[s]) {
+            OPOSE_HIP_CHECK(pooled_stream(&h->sstream[s], 0));
+            OPOSE_HIP_CHECK(hipEventCreateWithFlags(&h->ev_join[s], hipEventDisableTiming));
+        }
+        OPOSE_HIP_CHECK(hipStreamWaitEvent(h->sstream[s], h->ev_fork, 0));
+    }
+    // largest scale first: it is the critical path
+    {
+        Redirect<hipStream_t> stream(h->stream);
+        for (int s = ns - 1; s >= 0; --s) {
+            h->stream = s ? h->sstream[s] : main;
+            h->slot = s;
+            fn(s);
+            if (s) OPOSE_HIP_CHECK(hipEventRecord(h->ev_join[s], h->sstream[s]));
+        }
+    }
+    for (int s = 1; s < ns; ++s) OPOSE_HIP_CHECK(hipStreamWaitEvent(main, h->ev_join[s], 0));
+}
+
+// Every scale's network in lockstep on the handle's stream (split-bf16 path): per scale the
+// preprocess into its slot's input, one conv launch per layer for all scales (hand_net_x6 /
+// body_net_x6 segments), per scale the x8 upsample of its C heat / PAF channels into mid(s).
+static void run_scales_lockstep(opose_ctx* h, int net, const uint8_t* fd, int64_t frame_stride, int64_t row_stride,
+                                int N, int H, int W, const std::vector<ScaleGeom>& gs, const opose_params& p) {
+    if (!h->loaded[net]) throw std::runtime_error(net == OPOSE_NET_BODY ? "body weights not loaded" : "hand weights not loaded");
+    std::vector<NetSeg> segs;
+    for (size_t s = 0; s < gs.size(); ++s) {
+        const ScaleGeom& g = gs[s];
+        float* x = h->ws[s].x.ensure<float>((size_t)N * 3 * g.Hp * g.Wp, h->stream);
+        ProfEntry pe;
+        h->prof_begin(pe, "preprocess", 0, (double)N * (3.0 * H * W + 12.0 * g.Hp * g.Wp));
+        preprocess_scale(fd, frame_stride, row_stride, N, H, W, g, p, x, h->stream);
+        h->prof_end(pe);
+        segs.push_back(NetSeg{x, N, g.Hp, g.Wp, (int)s});
+    }
+    const std::vector<float*> outs = net == OPOSE_NET_BODY ? body_net_x6(h, segs) : hand_net_x6(h, segs);
+    for (size_t s = 0; s < gs.size(); ++s)
+        if (net == OPOSE_NET_BODY)
+            body_to_mid(h, (int)s, outs[s], 185, N, gs[s]);
+        else
+            upsample_to_mid(h, (int)s, outs[s], 150, N, gs[s], 21);
+}
+
+static void pipelined_body(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs,
+                           const opose_params& p, uint8_t* rec, const std::function<void()>& net_part,
+                           bool defer) {
+    if (h->dpost.pending && !(h->dpost.N == N && h->dpost.H == H && h->dpost.W == W)) flush_post(h);
+    if (!h->nstream) {
+        int lo = 0, hi = 0;
+        OPOSE_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        // the network stream gets the higher priority: its conv grids should not wait for
+        // post-network workgroups that can run on whatever CUs are left (network high / post
+        // high / both default measured the same)
+        OPOSE_HIP_CHECK(pooled_stream(&h->nstream, hi));
+        h->nstream_prio = hi;
+        for (hipEvent_t* e : {&h->ev_net, &h->ev_main, &h->ev_post[0], &h->ev_post[1], &h->ev_gate})
+            OPOSE_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    const int set = h->next_set;
+    h->next_set ^= 1;
+    if (h->post_pending[set]) OPOSE_HIP_CHECK(hipStreamWaitEvent(h->nstream, h->ev_post[set], 0));
+    if (h->main_dirty) {
+        OPOSE_HIP_CHECK(hipEventRecord(h->ev_main, h->stream));
+        OPOSE_HIP_CHECK(hipStreamWaitEvent(h->nstream, h->ev_main, 0));
+        h->main_dirty = false;
+    }
+    hipStream_t main = h->stream;
+    const bool gate = h->dpost.pending;  // the previous call's post waits for this network's gate
+    {
+        Redirect<int> mid_set(h->mid_set, set);
+        Redirect<hipStream_t> stream(h->stream, h->nstream);
+        Redirect<hipEvent_t> gate_ev(h->gate_ev, gate ? h->ev_gate : nullptr);
+        h->gate_done = false;
+        net_part();
+        if (gate && !h->gate_done) OPOSE_HIP_CHECK(hipEventRecord(h->ev_gate, h->nstream));
+    }
+    // ev_net is re-recorded every call: take the gate first (the deferred post's network ran
+    // before this one on nstream, so the gate implies it)
+    if (gate) enqueue_deferred_post(h, h->ev_gate);
+    OPOSE_HIP_CHECK(hipEventRecord(h->ev_net, h->nstream));
+    if (defer) {
+        opose_ctx::DeferredPost& d = h->dpost;
+        d.pending = true;
+        d.N = N;
+        d.H = H;
+        d.W = W;
+        d.set = set;
+        d.gs = gs;
+        d.p = p;
+        d.rec = rec;
+        return;
+    }
+    OPOSE_HIP_CHECK(hipStreamWaitEvent(main, h->ev_net, 0));
+    Redirect<int> mid_set(h->mid_set, set);
+    body_post_common(h, N, H, W, gs, p, rec);
+    OPOSE_HIP_CHECK(hipEventRecord(h->ev_post[set], main));
+    h->post_pending[set] = true;
+}
+
+// bytes of one direction of a band's halo exchange at wl columns: 3 pieces x 32 groups (the
+// widest stage tensor, 256 channels) x 3 rows x P units x 16 B
+static size_t band_halo_bytes(int wl) { return (size_t)3 * 32 * 3 * x6p_pitch(wl) * 16; }
+
+}  // namespace opose
+
+using namespace opose;
+
+static int net_forward(opose_t* h, int net, const float* x, int N, int Hp, int Wp, float* o1, float* o2, int flags) {
+    if (!h || !x || N <= 0 || Hp < 8 || Wp < 8 || Hp % 8 || Wp % 8) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const size_t in_n = (size_t)N * 3 * Hp * Wp;
+        const float* xd = x;
+        if (!(flags & OPOSE_IN_DEVICE)) {
+            float* buf = h->w().x.ensure<float>(in_n, h->stream);
+            OPOSE_HIP_CHECK(hipMemcpyAsync(buf, x, in_n * 4, hipMemcpyHostToDevice, h->stream));
+            xd = buf;
+        }
+        const int hl = Hp / 8, wl = Wp / 8;
+        const size_t plane = (size_t)hl * wl;
+        const hipMemcpyKind kind = (flags & OPOSE_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (net == OPOSE_NET_BODY) {
+            float* S = body_net(h, xd, N, Hp, Wp);
+            // S: [N][185][hl][wl]; paf = ch 0..37, heat = 38..56
+            OPOSE_HIP_CHECK(hipMemcpy2DAsync(o1, 38 * plane * 4, S, 185 * plane * 4, 38 * plane * 4, N, kind, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpy2DAsync(o2, 19 * plane * 4, S + 38 * plane, 185 * plane * 4, 19 * plane * 4, N,
+                                             kind, h->stream));
+        } else {
+            float* S = hand_net(h, xd, N, Hp, Wp);
+            OPOSE_HIP_CHECK(hipMemcpy2DAsync(o1, 22 * plane * 4, S, 150 * plane * 4, 22 * plane * 4, N, kind, h->stream));
+        }
+        if (!(flags & OPOSE_OUT_DEVICE)) OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_hand_forward_pyramid(opose_t* h, int n, const float* const* xs, const int* N, const int* Hp, const int* Wp,
+                               float* const* heats, int flags) {
+    if (!h || !xs || !N || !Hp || !Wp || !heats || n < 1 || n > OPOSE_MAX_SCALES) return OPOSE_E_ARG;
+    for (int i = 0; i < n; ++i)
+        if (!xs[i] || !heats[i] || N[i] <= 0 || Hp[i] < 8 || Wp[i] < 8 || Hp[i] % 8 || Wp[i] % 8) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        if (!h->loaded[OPOSE_NET_HAND]) throw std::runtime_error("hand weights not loaded");
+        const hipMemcpyKind kind = (flags & OPOSE_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        std::vector<NetSeg> segs;
+        for (int i = 0; i < n; ++i) {
+            const size_t in_n = (size_t)N[i] * 3 * Hp[i] * Wp[i];
+            const float* xd = xs[i];
+            if (!(flags & OPOSE_IN_DEVICE)) {
+                float* buf = h->ws[i].x.ensure<float>(in_n, h->stream);
+                OPOSE_HIP_CHECK(hipMemcpyAsync(buf, xs[i], in_n * 4, hipMemcpyHostToDevice, h->stream));
+                xd = buf;
+            }
+            segs.push_back(NetSeg{xd, N[i], Hp[i], Wp[i], i});
+        }
+        std::vector<float*> outs;
+        if (h->x6) {
+            outs = hand_net_x6(h, segs);
+        } else {
+            Redirect<int> slot(h->slot);
+            for (int i = 0; i < n; ++i) {
+                h->slot = i;
+                outs.push_back(hand_net(h, segs[i].x, N[i], Hp[i], Wp[i]));
+            }
+        }
+        for (int i = 0; i < n; ++i) {
+            const size_t plane = (size_t)(Hp[i] / 8) * (Wp[i] / 8);
+            OPOSE_HIP_CHECK(hipMemcpy2DAsync(heats[i], 22 * plane * 4, outs[i], 150 * plane * 4, 22 * plane * 4, N[i],
+                                             kind, h->stream));
+        }
+        if (!(flags & OPOSE_OUT_DEVICE)) OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_body_forward(opose_t* h, const float* x, int N, int Hp, int Wp, float* paf, float* heat, int flags) {
+    if (!paf || !heat) return OPOSE_E_ARG;
+    return net_forward(h, OPOSE_NET_BODY, x, N, Hp, Wp, paf, heat, flags);
+}
+
+int opose_hand_forward(opose_t* h, const float* x, int N, int Hp, int Wp, float* heat, int flags) {
+    if (!heat) return OPOSE_E_ARG;
+    return net_forward(h, OPOSE_NET_HAND, x, N, Hp, Wp, heat, nullptr, flags);
+}
+
+int opose_body_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride, int64_t frame_stride,
+                     const opose_params* pp, void* records, int flags) {
+    if (!h || !bgr || !records || N <= 0 || H <= 0 || W <= 0) return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        OPOSE_HIP_CHECK(hipSetDevice(h->device));  // pipelined or not: decided below
+        const opose_params p = fill_params(pp, OPOSE_NET_BODY);
+        const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, flags);
+        std::vector<ScaleGeom> gs;
+        for (int s = 0; s < p.n_scales; ++s) gs.push_back(geom(p.scales[s], p, H, W));
+        uint8_t* rec = records_dest(h, N, records, flags);
+        auto scale_net = [&](int s) {
+            const ScaleGeom& g = gs[s];
+            float* x = h->w().x.ensure<float>((size_t)N * 3 * g.Hp * g.Wp, h->stream);
+            ProfEntry pe;
+            h->prof_begin(pe, "preprocess", 0, (double)N * (3.0 * H * W + 12.0 * g.Hp * g.Wp));
+            preprocess_scale(fd, frame_stride, row_stride, N, H, W, g, p, x, h->stream);
+            h->prof_end(pe);
+            float* S = body_net(h, x, N, g.Hp, g.Wp);
+            body_to_mid(h, s, S, 185, N, g);
+        };
+        const bool lockstep = h->x6 && h->lockstep && p.n_scales > 1;
+        auto net_part = [&] {
+            if (lockstep)
+                run_scales_lockstep(h, OPOSE_NET_BODY, fd, frame_stride, row_stride, N, H, W, gs, p);
+            else if (h->scale_streams && p.n_scales > 1)  // (pipelined: forked from and joined into nstream)
+                run_scales_concurrently(h, p.n_scales, scale_net);
+            else
+                for (int s = 0; s < p.n_scales; ++s) scale_net(s);
+        };
+        if ((flags & OPOSE_PIPELINE) && (flags & OPOSE_IN_DEVICE) && (flags & OPOSE_OUT_DEVICE)) {
+            pipelined_body(h, N, H, W, gs, p, rec, net_part, (flags & OPOSE_PIPELINE_DEFER) != 0);
+        } else if (!lockstep && h->scale_streams && p.n_scales > 1) {  // multi-scale pyramid (C5): scales concurrently
+            enter_main(h);
+            h->mid_set = 0;
+            run_scales_concurrently(h, p.n_scales, scale_net);
+            body_post_common(h, N, H, W, gs, p, rec);
+        } else {
+            enter_main(h);
+            h->mid_set = 0;
+            const std::string key = call_key("body", N, H, W, row_stride, frame_stride, p, fd, rec, h->ppp, h->maxp);
+            run_graphed(h, key, [&] {
+                net_part();
+                body_post_common(h, N, H, W, gs, p, rec);
+            });
+        }
+        return finish_records(h, N, records, rec, flags);
+    });
+}
+
+int opose_body_post(opose_t* h, const float* maps, int N, int hl, int wl, int pad_down, int pad_right, int H, int W,
+                    const opose_params* pp, void* records, int flags) {
+    if (!h || !maps || !records || N <= 0 || hl <= 0 || wl <= 0 || H <= 0 || W <= 0) return OPOSE_E_ARG;
+    if (pad_down < 0 || pad_right < 0 || pad_down >= 8 * hl || pad_right >= 8 * wl) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        opose_params p = fill_params(pp, OPOSE_NET_BODY);
+        p.n_scales = 1;
+        const float* md = stage_maps(h, maps, (size_t)N * 57 * hl * wl, flags);
+        const ScaleGeom g = geom_from_pads(hl, wl, pad_down, pad_right, H, W);
+        body_to_mid(h, 0, md, 57, N, g);
+        uint8_t* rec = records_dest(h, N, records, flags);
+        body_post_common(h, N, H, W, {g}, p, rec);
+        return finish_records(h, N, records, rec, flags);
+    });
+}
+
+// ---- scale-sharded single-frame latency ---------------------------------
+int opose_body_scale_geom(int H, int W, const opose_params* pp, int s, int* out4) {
+    if (!out4 || H <= 0 || W <= 0) return OPOSE_E_ARG;
+    try {
+        const opose_params p = fill_params(pp, OPOSE_NET_BODY);
+        if (s < 0 || s >= p.n_scales) return OPOSE_E_ARG;
+        const ScaleGeom g = geom(p.scales[s], p, H, W);
+        out4[0] = g.hl;
+        out4[1] = g.wl;
+        out4[2] = g.Hp - g.Hs;
+        out4[3] = g.Wp - g.Ws;
+        return OPOSE_OK;
+    } catch (const std::exception&) {
+        return OPOSE_E_SHAPE;
+    }
+}
+
+int opose_body_scale_maps(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                          int64_t frame_stride, const opose_params* pp, int s, float* maps, int flags) {
+    if (!h || !bgr || !maps || N <= 0 || H <= 0 || W <= 0) return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const opose_params p = fill_params(pp, OPOSE_NET_BODY);
+        if (s < 0 || s >= p.n_scales) return OPOSE_E_ARG;
+        const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, flags);
+        const ScaleGeom g = geom(p.scales[s], p, H, W);
+        float* x = h->w().x.ensure<float>((size_t)N * 3 * g.Hp * g.Wp, h->stream);
+        preprocess_scale(fd, frame_stride, row_stride, N, H, W, g, p, x, h->stream);
+        const float* S = body_net(h, x, N, g.Hp, g.Wp);
+        // channels 0..56 of the stage-6 concat buffer [N][185][hl*wl] -> [N][57][hl*wl]
+        const size_t plane = (size_t)g.hl * g.wl * 4;
+        OPOSE_HIP_CHECK(hipMemcpy2DAsync(maps, 57 * plane, S, 185 * plane, 57 * plane, N,
+                                         (flags & OPOSE_OUT_DEVICE) ? hipMemcpyDeviceToDevice
+                                                                    : hipMemcpyDeviceToHost,
+                                         h->stream));
+        if (!(flags & OPOSE_OUT_DEVICE)) OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        return OPOSE_OK;
+    });
+}
+
+size_t opose_body_band_halo_bytes(int wl) { return wl > 0 ? band_halo_bytes(wl) : 0; }
+
+int opose_body_band_maps(opose_t* h, const uint8_t* bgr, int H, int W, int64_t row_stride, const opose_params* pp,
+                         int s, int r0, int r1, float* maps, opose_halo_fn fn, void* user, void* xbuf,
+                         size_t xbuf_bytes, int flags) {
+    if (!h || !bgr || !maps || !xbuf || H <= 0 || W <= 0 || row_stride < (int64_t)W * 3) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const opose_params p = fill_params(pp, OPOSE_NET_BODY);
+        if (s < 0 || s >= p.n_scales) return OPOSE_E_ARG;
+        const ScaleGeom g = geom(p.scales[s], p, H, W);
+        if (r0 < 0 || r1 > g.hl || r1 - r0 < 3) return OPOSE_E_ARG;
+        if (!fn && ((r0 > 0 && (!h->comm || h->band_up < 0)) || (r1 < g.hl && (!h->comm || h->band_dn < 0))))
+            return OPOSE_E_ARG;  // the library's exchange needs opose_rccl_init + opose_set_band_peers
+        if (xbuf_bytes < 4 * band_halo_bytes(g.wl)) return OPOSE_E_ARG;
+        if (!h->x6) throw std::invalid_argument("row bands need the split-bf16 path (OPOSE_CONV=f32 is set)");
+        if (!h->loaded[OPOSE_NET_BODY]) throw std::runtime_error("body weights not loaded");
+        const uint8_t* fd = stage_frames(h, bgr, 1, H, W, row_stride, row_stride * H, flags);
+        const int hb = r1 - r0;
+        float* out = (flags & OPOSE_OUT_DEVICE) ? maps : h->maps_in.ensure<float>((size_t)57 * hb * g.wl, h->stream);
+        float* x = h->w().x.ensure<float>((size_t)3 * g.Hp * g.Wp, h->stream);
+        preprocess_scale(fd, row_stride * H, row_stride, 1, H, W, g, p, x, h->stream);
+        const size_t cap = xbuf_bytes / 4;
+        const Band band{r0, r1, out, fn, user, static_cast<uint8_t*>(xbuf), cap};
+        body_net_x6(h, {NetSeg{x, 1, g.Hp, g.Wp, h->slot}}, &band);
+        if (!(flags & OPOSE_OUT_DEVICE)) {
+            OPOSE_HIP_CHECK(hipMemcpyAsync(maps, out, (size_t)57 * hb * g.wl * 4, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        return OPOSE_OK;
+    });
+}
+
+int opose_body_post_scales(opose_t* h, const float* const* maps, const int* hl, const int* wl, const int* pad_down,
+                           const int* pad_right, int n_scales, int N, int H, int W, const opose_params* pp,
+                           void* records, int flags) {
+    if (!h || !maps || !hl || !wl || !pad_down || !pad_right || !records || N <= 0 || H <= 0 || W <= 0 ||
+        n_scales < 1 || n_scales > OPOSE_MAX_SCALES)
+        return OPOSE_E_ARG;
+    for (int s = 0; s < n_scales; ++s)
+        if (!maps[s] || hl[s] <= 0 || wl[s] <= 0 || pad_down[s] < 0 || pad_right[s] < 0 ||
+            pad_down[s] >= 8 * hl[s] || pad_right[s] >= 8 * wl[s])
+            return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        opose_params p = fill_params(pp, OPOSE_NET_BODY);
+        std::vector<ScaleGeom> gs;
+        for (int s = 0; s < n_scales; ++s) {
+            const ScaleGeom g = geom_from_pads(hl[s], wl[s], pad_down[s], pad_right[s], H, W);
+            const float* md = stage_maps(h, maps[s], (size_t)N * 57 * g.hl * g.wl, flags);
+            body_to_mid(h, s, md, 57, N, g);
+            gs.push_back(g);
+        }
+        uint8_t* rec = records_dest(h, N, records, flags);
+        body_post_common(h, N, H, W, gs, p, rec);
+        return finish_records(h, N, records, rec, flags);
+    });
+}
+
+int opose_batch_body_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                           int64_t frame_stride, const opose_params* pp, void* records, int flags) {
+    if (!h || !bgr || !records || N <= 0 || H <= 0 || W <= 0) return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const opose_params p = fill_params(pp, OPOSE_NET_BODY);
+        // Batch_body.calculate_size_pad (srcmx/Batch_model.py:302-307): int() truncation
+        const double scale = p.boxsize * p.scales[0] / H;
+        const int nh = (int)(H * scale), nw = (int)(W * scale);
+        if (nh <= 0 || nw <= 0) throw std::invalid_argument("scale produces an empty image");
+        const int Hp = round_up(nh, p.stride), Wp = round_up(nw, p.stride);
+        const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, flags);
+        uint8_t* rec = records_dest(h, N, records, flags);
+        const std::string key = call_key("batch_body", N, H, W, row_stride, frame_stride, p, fd, rec, h->ppp, h->maxp);
+        run_graphed(h, key, [&] {
+            float* x = h->w().x.ensure<float>((size_t)N * 3 * Hp * Wp, h->stream);
+            ProfEntry pe;
+            h->prof_begin(pe, "preprocess", 0, (double)N * (3.0 * H * W + 12.0 * Hp * Wp));
+            const float sc = (float)(1.0 / scale);  // torch: float(1 / scale_factor)
+            launch_preprocess_torch(fd, frame_stride, row_stride, N, H, W, nh, nw, sc, sc, Hp, Wp, x, h->stream);
+            h->prof_end(pe);
+            float* S = body_net(h, x, N, Hp, Wp);
+            batch_post_common(h, N, H, W, S, 185, Hp / 8, Wp / 8, nh, nw, p, rec);
+        });
+        return finish_records(h, N, records, rec, flags);
+    });
+}
+
+int opose_batch_body_post(opose_t* h, const float* maps, int N, int hl, int wl, int nh, int nw, int H, int W,
+                          const opose_params* pp, void* records, int flags) {
+    if (!h || !maps || !records || N <= 0 || hl <= 0 || wl <= 0 || H <= 0 || W <= 0) return OPOSE_E_ARG;
+    if (nh <= 0 || nw <= 0 || nh > 8 * hl || nw > 8 * wl) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const opose_params p = fill_params(pp, OPOSE_NET_BODY);
+        const float* md = stage_maps(h, maps, (size_t)N * 57 * hl * wl, flags);
+        uint8_t* rec = records_dest(h, N, records, flags);
+        batch_post_common(h, N, H, W, md, 57, hl, wl, nh, nw, p, rec);
+        return finish_records(h, N, records, rec, flags);
+    });
+}
+
+int opose_hand_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride, int64_t frame_stride,
+                     const opose_params* pp, double* peaks, int32_t* found, int flags) {
+    if (!h || !bgr || !peaks || !found || N <= 0 || H <= 0 || W <= 0) return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const opose_params p = fill_params(pp, OPOSE_NET_HAND);
+        const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, flags);
+        std::vector<ScaleGeom> gs;
+        for (int s = 0; s < p.n_scales; ++s) gs.push_back(geom(p.scales[s], p, H, W));
+        const bool od = flags & OPOSE_OUT_DEVICE;
+        char fk[32];
+        std::snprintf(fk, sizeof fk, "%p", od ? (const void*)found : nullptr);
+        const std::string key =
+            call_key("hand", N, H, W, row_stride, frame_stride, p, fd, od ? (const void*)peaks : nullptr, 0, 0) + fk;
+        auto scale_net = [&](int s) {
+            const ScaleGeom& g = gs[s];
+            float* x = h->w().x.ensure<float>((size_t)N * 3 * g.Hp * g.Wp, h->stream);
+            ProfEntry pe;
+            h->prof_begin(pe, "preprocess", 0, (double)N * (3.0 * H * W + 12.0 * g.Hp * g.Wp));
+            preprocess_scale(fd, frame_stride, row_stride, N, H, W, g, p, x, h->stream);
+            h->prof_end(pe);
+            float* Sb = hand_net(h, x, N, g.Hp, g.Wp);
+            upsample_to_mid(h, s, Sb, 150, N, g, 21);
+        };
+        if (h->x6 && h->lockstep && p.n_scales > 1) {
+            run_graphed(h, key, [&] {
+                run_scales_lockstep(h, OPOSE_NET_HAND, fd, frame_stride, row_stride, N, H, W, gs, p);
+                hand_post_common(h, N, H, W, gs, p, peaks, found, flags & OPOSE_OUT_DEVICE);
+            });
+        } else if (h->scale_streams && p.n_scales > 1) {
+            // the scales' networks are independent until the heat average: each on its own stream
+            // with its own workspace (a single crop's layers fill a fraction of the chip each)
+            run_scales_concurrently(h, p.n_scales, scale_net);
+            hand_post_common(h, N, H, W, gs, p, peaks, found, flags & OPOSE_OUT_DEVICE);
+        } else {
+            run_graphed(h, key, [&] {
+                for (int s = 0; s < p.n_scales; ++s) scale_net(s);
+                hand_post_common(h, N, H, W, gs, p, peaks, found, flags & OPOSE_OUT_DEVICE);
+            });
+        }
+        hand_finish(h, N, peaks, found, flags & OPOSE_OUT_DEVICE);
+    });
+    return OPOSE_OK;
+}
+
+int opose_batch_hand_post(opose_t* h, const float* maps, int N, int hl, int wl, const opose_params* pp, double* peaks,
+                          int32_t* found, int flags) {
+    if (!h || !maps || !peaks || !found || N <= 0 || hl <= 0 || wl <= 0) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const opose_params p = fill_params(pp, OPOSE_NET_HAND);
+        const float* md = stage_maps(h, maps, (size_t)N * 22 * hl * wl, flags);
+        batch_hand_post_common(h, N, 8 * hl, 8 * wl, md, 22, p, peaks, found, flags);
+    });
+    return OPOSE_OK;
+}
+
+int opose_batch_hand_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                           int64_t frame_stride, const opose_params* pp, double* peaks, int32_t* found, int flags) {
+    if (!h || !bgr || !peaks || !found || N <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const opose_params p = fill_params(pp, OPOSE_NET_HAND);
+        const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, flags);
+        // ToTensor - 0.5 at scale 1 (torch bicubic at scale 1 is the identity)
+        float* x = h->w().x.ensure<float>((size_t)N * 3 * H * W, h->stream);
+        ProfEntry pe;
+        h->prof_begin(pe, "preprocess", 0, (double)N * 15.0 * H * W);
+        launch_preprocess_torch(fd, frame_stride, row_stride, N, H, W, H, W, 1.f, 1.f, H, W, x, h->stream);
+        h->prof_end(pe);
+        float* Sb = hand_net(h, x, N, H, W);
+        batch_hand_post_common(h, N, H, W, Sb, 150, p, peaks, found, flags);
+    });
+    return OPOSE_OK;
+}
+
+int opose_hand_infer_crops(opose_t* h, const uint8_t* const* crops, const int* sizes, const int64_t* row_strides,
+                           int n, const opose_params* pp, double* peaks, int32_t* found, int flags) {
+    if (!h || !crops || !sizes || !row_strides || !peaks || !found || n <= 0) return OPOSE_E_ARG;
+    for (int i = 0; i < n; ++i)
+        if (!crops[i] || sizes[i] <= 0 || row_strides[i] < (int64_t)sizes[i] * 3) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const opose_params p = fill_params(pp, OPOSE_NET_HAND);
+        const int ns = p.n_scales;
+        // per-crop geometry; the network side (Hs, Ws, Hp, Wp per scale) must agree across crops
+        std::vector<std::vector<ScaleGeom>> gs(n);
+        for (int i = 0; i < n; ++i)
+            for (int s = 0; s < ns; ++s) gs[i].push_back(geom(p.scales[s], p, sizes[i], sizes[i]));
+        for (int i = 1; i < n; ++i)
+            for (int s = 0; s < ns; ++s)
+                if (gs[i][s].Hs != gs[0][s].Hs || gs[i][s].Ws != gs[0][s].Ws)
+                    throw std::invalid_argument("crops do not share the network input size of a scale");
+        // stage the crops (host -> one device buffer)
+        std::vector<size_t> off(n + 1, 0);
+        for (int i = 0; i < n; ++i) off[i + 1] = off[i] + (size_t)row_strides[i] * sizes[i];
+        uint8_t* buf = nullptr;
+        if (!(flags & OPOSE_IN_DEVICE)) {
+            buf = h->frames.ensure<uint8_t>(off[n], h->stream);
+            for (int i = 0; i < n; ++i)
+                OPOSE_HIP_CHECK(hipMemcpyAsync(buf + off[i], crops[i], host_span(1, sizes[i], sizes[i], row_strides[i], 0),
+                                               hipMemcpyHostToDevice, h->stream));
+        }
+        // all crops of a scale form one batch; with the split-bf16 path all scales run in lockstep
+        // (one conv launch per layer for every crop and scale).  Batches are cut so that the
+        // largest activation (64 channels at the largest scale's full resolution, X6: 3 x 128 B
+        // per pixel) stays below the 2 GiB the conv kernels address with 32-bit offsets.
+        const bool lockstep = h->x6 && h->lockstep && ns > 1;
+        if (lockstep && !h->loaded[OPOSE_NET_HAND]) throw std::runtime_error("hand weights not loaded");
+        size_t maxpix = 0;
+        for (int s = 0; s < ns; ++s) maxpix = std::max(maxpix, (size_t)gs[0][s].Hp * gs[0][s].Wp);
+        const int chunk = (int)std::max<size_t>(1, (((size_t)1 << 31) - 1) / (3 * 128 * maxpix));
+        // size every per-crop buffer for the largest crop / all crops up front: a reallocation
+        // after the first batch would drop the results of the crops already done
+        const int wmax = *std::max_element(sizes, sizes + n);
+        h->avg.ensure<double>((size_t)21 * wmax * wmax, h->stream);
+        h->hlab.ensure<int>((size_t)21 * wmax * wmax, h->stream);
+        h->hsums.ensure<double>((size_t)21 * wmax * wmax, h->stream);
+        if (!(flags & OPOSE_OUT_DEVICE)) {
+            h->hpeaks.ensure<double>((size_t)n * 21 * 3, h->stream);
+            h->hfound.ensure<int>((size_t)n * 21, h->stream);
+        }
+        for (int c0 = 0; c0 < n; c0 += chunk) {
+            const int nc = std::min(chunk, n - c0);
+            std::vector<NetSeg> segs;
+            for (int s = 0; s < ns; ++s) {
+                const ScaleGeom& g0 = gs[0][s];
+                float* x = h->ws[lockstep ? s : h->slot].x.ensure<float>((size_t)nc * 3 * g0.Hp * g0.Wp, h->stream);
+                ProfEntry pe;
+                h->prof_begin(pe, "preprocess", 0, 0);
+                for (int i = c0; i < c0 + nc; ++i) {
+                    const ScaleGeom& g = gs[i][s];
+                    const uint8_t* src = buf ? buf + off[i] : crops[i];
+                    preprocess_scale(src, (int64_t)(off[i + 1] - off[i]), row_strides[i], 1, sizes[i], sizes[i], g, p,
+                                     x + (size_t)(i - c0) * 3 * g.Hp * g.Wp, h->stream);
+                }
+                h->prof_end(pe);
+                if (lockstep) {
+                    segs.push_back(NetSeg{x, nc, g0.Hp, g0.Wp, s});
+                    continue;
+                }
+                float* Sb = hand_net(h, x, nc, g0.Hp, g0.Wp);
+                upsample_to_mid(h, s, Sb, 150, nc, g0, 21);
+            }
+            if (lockstep) {
+                const std::vector<float*> outs = hand_net_x6(h, segs);
+                for (int s = 0; s < ns; ++s) upsample_to_mid(h, s, outs[s], 150, nc, gs[0][s], 21);
+            }
+            for (int i = c0; i < c0 + nc; ++i)
+                hand_post_common(h, 1, sizes[i], sizes[i], gs[i], p, peaks, found, flags & OPOSE_OUT_DEVICE, i - c0, i);
+        }
+        hand_finish(h, n, peaks, found, flags & OPOSE_OUT_DEVICE);
+    });
+    return OPOSE_OK;
+}
+
+int opose_hand_post(opose_t* h, const float* const* maps, const int* hl, const int* wl, const int* pad_down,
+                    const int* pad_right, int n_scales, int N, int H, int W, const opose_params* pp,
+                    double* peaks, int32_t* found, int flags) {
+    if (!h || !maps || !hl || !wl || !pad_down || !pad_right || !peaks || !found || N <= 0 || H <= 0 || W <= 0 ||
+        n_scales < 1 || n_scales > OPOSE_MAX_SCALES)
+        return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        opose_params p = fill_params(pp, OPOSE_NET_HAND);
+        std::vector<ScaleGeom> gs;
+        for (int s = 0; s < n_scales; ++s) {
+            const ScaleGeom g = geom_from_pads(hl[s], wl[s], pad_down[s], pad_right[s], H, W);
+            if (g.Hs <= 0 || g.Ws <= 0) throw std::invalid_argument("bad pad");
+            const float* md = stage_maps(h, maps[s], (size_t)N * 22 * g.hl * g.wl, flags);
+            upsample_to_mid(h, s, md, 22, N, g, 21);
+            gs.push_back(g);
+        }
+        hand_post_common(h, N, H, W, gs, p, peaks, found, flags & OPOSE_OUT_DEVICE);
+        hand_finish(h, N, peaks, found, flags & OPOSE_OUT_DEVICE);
+    });
+    return OPOSE_OK;
+}
+

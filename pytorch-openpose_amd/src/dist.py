@@ -91,7 +91,7 @@ def scale_plan(costs, world: int):
 # own rows, exchanging 3 halo rows with its neighbours before each 3x3 / 7x7 stage layer (the
 # stages' receptive field, 84 rows at H/8, rules out recomputing theirs).
 TRUNK_FRAC = 0.30
-BAND_MARGIN = 10  # output rows (engine.cpp kBandTrunkMargin)
+BAND_MARGIN = 10  # output rows (engine_net.cpp kBandTrunkMargin)
 # per banded piece: a fraction of the scale's work (lower grid fill of the band's smaller
 # layers) plus a fixed latency in output pixels (~0.5 ms: 54 pack / unpack launches, 27 halo
 # callbacks, per-launch costs of the band's ~90 launches); fitted to one MI355X

@@ -1,5 +1,5 @@
 // Standalone HIP repro of the round-4 hipGraphLaunch segfault: no libopose.
-// It follows engine.cpp's order: run_graphed (eager first sighting, capture on the second,
+// It follows engine_api.cpp's order: run_graphed (eager first sighting, capture on the second,
 // replay after) over run_scales_concurrently's fork (event record on the main stream, the side
 // stream waits, work on both, join back), and release() (drain, destroy the graph executables,
 // destroy the events, return the side and main streams to a process-wide pool).

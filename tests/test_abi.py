@@ -41,6 +41,22 @@ def test_python_binding_covers_header():
     assert sorted(_native.EXPORTED) == declared_symbols()
 
 
+def test_null_handle_is_an_argument_error_everywhere():
+    """Every export that returns int and takes the handle first answers a null handle (every other
+    argument zero or null) with OPOSE_E_ARG, before it touches HIP: an entry point lost or linked
+    to the wrong definition when the runtime's sources are rearranged does not."""
+    from src import _native
+    checked = []
+    for name in _native.EXPORTED:
+        fn = getattr(_native.lib, name)
+        if fn.restype is not ctypes.c_int or not fn.argtypes or fn.argtypes[0] is not ctypes.c_void_p:
+            continue
+        rc = fn(*[t() for t in fn.argtypes])  # a default-constructed ctypes value is 0 / NULL
+        assert rc == _native.OPOSE_E_ARG, (name, rc)
+        checked.append(name)
+    assert len(checked) >= 37, checked
+
+
 def test_default_params_are_reference_constants():
     from src import _native
     p = _native.default_params(_native.NET_BODY)
