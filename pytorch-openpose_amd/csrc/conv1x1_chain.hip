@@ -39,8 +39,6 @@ __device__ __forceinline__ int chain_group_of(const X6ChainArgs& a, int tile) {
 
 __global__ __launch_bounds__(256) void conv1x1_chain_x6(X6ChainArgs a) {
     constexpr int PT = kChainPT;
-    constexpr int PA[6] = {0, 0, 0, 1, 2, 1};
-    constexpr int PB[6] = {2, 0, 1, 0, 0, 1};
     // intermediate slice: [piece][16 groups][64 pixels] units
     __shared__ __attribute__((aligned(16))) uint4 hs[3 * 16 * PT];
 
@@ -72,10 +70,6 @@ __global__ __launch_bounds__(256) void conv1x1_chain_x6(X6ChainArgs a) {
     const __amdgpu_buffer_rsrc_t w2r = __builtin_amdgcn_make_buffer_rsrc((void*)G.w2, (short)0, 0x7fffffff, 0x00020000);
     auto bld = [](__amdgpu_buffer_rsrc_t r, uint32_t vo, uint32_t so) __attribute__((always_inline)) {
         return __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)vo, (int)so, 0));
-    };
-    auto mfma = [](const i32x4& x, const i32x4& y, f32x4 c) __attribute__((always_inline)) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, x), __builtin_bit_cast(bf16x8, y), c,
-                                                       0, 0, 0);
     };
 
     f32x4 acc2[4];
@@ -113,7 +107,7 @@ __global__ __launch_bounds__(256) void conv1x1_chain_x6(X6ChainArgs a) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc1[i][j] = mfma(fa[PA[t]][i], fb[c & 1][PB[t]][j], acc1[i][j]);
+                    for (int j = 0; j < 4; ++j) acc1[i][j] = mfma_x6(fa[kPieceA[t]][i], fb[c & 1][kPieceB[t]][j], acc1[i][j]);
         }
         // the second conv's weight fragments for this slice (4 k chunks), in flight during the
         // epilogue below
@@ -134,18 +128,13 @@ __global__ __launch_bounds__(256) void conv1x1_chain_x6(X6ChainArgs a) {
                 float v[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) v[t] = fmaxf(acc1[i][j][t] + G.b1[mc * 128 + rl + t], 0.f);
-                uint32_t h[3][4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) split3(v[t], h[0][t], h[1][t], h[2][t]);
+                uint2 w[3];
+                pack_pieces4(v, w);
                 const int px = 16 * j + l16;
 #pragma unroll
-                for (int pc = 0; pc < 3; ++pc) {
-                    uint2 w;
-                    w.x = h[pc][0] | (h[pc][1] << 16);
-                    w.y = h[pc][2] | (h[pc][3] << 16);
+                for (int pc = 0; pc < 3; ++pc)
                     *reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(&hs[(pc * 16 + (rl >> 3)) * PT + px]) +
-                                              ((rl >> 2) & 1) * 8) = w;
-                }
+                                              ((rl >> 2) & 1) * 8) = w[pc];
             }
         }
         __syncthreads();
@@ -161,12 +150,12 @@ __global__ __launch_bounds__(256) void conv1x1_chain_x6(X6ChainArgs a) {
 #pragma unroll
             for (int t = 0; t < 6; ++t)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc2[j] = mfma(fw[s][PA[t]], fh[PB[t]][j], acc2[j]);
+                for (int j = 0; j < 4; ++j) acc2[j] = mfma_x6(fw[s][kPieceA[t]], fh[kPieceB[t]][j], acc2[j]);
         }
     }
 
     // ---- epilogue: bias (+ ReLU), X6 slice or fp32 NCHW channels
-    const int cout8 = (G.cout2 + 7) & ~7;
+    const X6Out out = x6_out(G);
     const int mq = 16 * wave + 4 * gi;  // first of 4 consecutive output channels
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -179,15 +168,7 @@ __global__ __launch_bounds__(256) void conv1x1_chain_x6(X6ChainArgs a) {
             v[t] = acc2[j][t] + (mq + t < G.cout2 ? G.b2[mq + t] : 0.f);
             if (G.relu2) v[t] = fmaxf(v[t], 0.f);
         }
-        if (G.out_f32) {
-            float* ob = static_cast<float*>(G.out) + ((size_t)n * G.out_c + G.out_off) * HW + rem;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                if (mq + t < G.cout2) ob[(size_t)(mq + t) * HW] = v[t];
-        } else if (mq < cout8) {
-            store4_x6(static_cast<uint8_t*>(G.out) + (size_t)x6_unit(G.out_l, n, mq >> 3, y, x) * 16 + ((mq >> 2) & 1) * 8,
-                      G.out_ps, v);
-        }
+        x6_store_quad(out, n, y, x, rem, HW, mq, v);
     }
 }
 

@@ -14,9 +14,11 @@
 //    weights are packed in this order (x6_pack_weights_pairs).  A chunk may span two channel
 //    groups: two window buffers, group g in buffer g & 1, the window of group g + 2 DMA'd right
 //    after the barrier of the last chunk that reads group g (>= 10 chunks before its first use).
-//  * Everything else is conv_x6's MODE-2 loop: 128 x 256 tile, 8 waves of 64 x 64, weights by
-//    LDS-DMA into two stages, six piece products per chunk in the order
-//    (0,2) (0,0) (0,1) | barrier | (1,0) (2,0) (1,1), fragments refilled after their last use.
+//  * The chunk loop is the one conv_x6 runs (x6_loop.h: six piece products per chunk around one
+//    barrier, fragments refilled after their last use), on a 128 x 256 tile, 8 waves of 64 x 64.
+//    Its own here: B fragments addressed per block in the window, weights alone by LDS-DMA into
+//    a ring of two or three stages, the window DMA right after the barrier, and the next chunk's
+//    fragment offsets computed in block 4's gaps.
 //  * Work units (tile, k slab): a group's tiles sum their chunks in `slabs` fixed ranges
 //    (common.h X6Group), so the order of every pixel's sum is set by the layer and the segment,
 //    not by the grid; a workgroup runs a list of units (data parallel: one whole tile), a slab
@@ -28,13 +30,11 @@
 //  * The same kernel runs the batched 3x3 convs on padded inputs (trunk conv3_x / conv4_x and
 //    the stage-1 CPM convs, src/model.py:41-62): a window per group serves 9 taps.
 #include <algorithm>
-#include <cstring>
 #include <stdexcept>
-#include <vector>
 
 #include "common.h"
 #include "kernels.h"
-#include "x6.h"
+#include "x6_loop.h"
 
 namespace opose {
 
@@ -68,15 +68,9 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_win_x6(X6Args a
     // two waves per SIMD: the younger half issues first when both are ready (guide T5, static form)
     if (NW == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
 
-    // this workgroup's work units (tile, k slab), XCD-contiguous ids (guide T1); a grid of one
-    // workgroup per whole tile is the data-parallel case
-    const int Gw = gridDim.x;
-    int id;
-    {
-        const int b = blockIdx.x, q = Gw >> 3, rr = Gw & 7, xcd = b & 7;
-        id = xcd * q + min(xcd, rr) + (b >> 3);
-    }
-    const X6Work wk = x6_work_of(a, id);
+    // this workgroup's work units (tile, k slab); a grid of one workgroup per whole tile is the
+    // data-parallel case
+    const X6Work wk = x6_work_of(a, x6_xcd_id());
     for (int k = wk.k0; k < wk.k1; ++k) {
     const int uid = wk.list ? wk.list[k] : k;
     const X6Unit un = x6_unit_of(a, uid);
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_win_x6(X6Args a
     const int ptl = (tile - G.t0) / nM;
     const int p0 = ptl * PT, m0 = mt * MT;
     __syncthreads();  // the previous piece's LDS reads are done
-    if (tid < MT) s_bias[tid] = (m0 + tid < G.cout) ? G.bias[m0 + tid] : 0.f;
+    x6_load_bias(s_bias, G, m0, MT);
 
     // ---- window geometry (wave-uniform): padded rows R of the tile's first / last pixel
     const int P = (int)G.in_l.rs;
@@ -115,16 +109,13 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_win_x6(X6Args a
                                                      src + (uint32_t)(64 * j + lane) * 16u, 0, 0, 0);
         }
     };
-    // weights: one buffer resource per chunk, the unit's row offset in soffset, lane * 16 in voffset
+    // weights: run u of this wave's A_PW (x6.h x6_dma_weights_unit), its row offset in soffset
     const uint32_t lane16 = (uint32_t)lane * 16u;
     auto dma_a_unit = [&](int c, int buf, int u) __attribute__((always_inline)) {
-        uint4* As = lds + buf * A_U;
         const int unit0 = (wave * A_PW + u) * 64;
         const int pg = unit0 / MT, m = unit0 - pg * MT;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(G.wt + (size_t)c * 12 * a.Mpad * 16), (short)0, (int)0x7fffffff, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(As + unit0), 16, lane16,
-                                                 (int)((uint32_t)(pg * a.Mpad + m0 + m) * 16u), 0, 0);
+        x6_dma_weights_unit(x6_weights_rsrc(G.wt, a.Mpad, c), (lds_units_t)(lds + buf * A_U), unit0, lane16,
+                            (uint32_t)(pg * a.Mpad + m0 + m) * 16u);
     };
     auto dma_a = [&](int c, int buf) __attribute__((always_inline)) {
 #pragma unroll
@@ -167,49 +158,16 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_win_x6(X6Args a
         for (int k = 0; k < OFF_STEPS; ++k) off_step(k);
     };
 
-    f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    i32x4 fa[3][TM], fb[3][TN];
-    constexpr int PA[6] = {0, 0, 0, 1, 2, 1};
-    constexpr int PB[6] = {2, 0, 1, 0, 0, 1};
-    constexpr int NB = TM * TN;
-    constexpr int TMN = TM + TN;
+    X6Frags<MT, TM, TN> f;
+    f.zero();
+    constexpr int NB = f.NB, TMN = f.TMN;
     const int a16 = (lane >> 4) * MT + wm0 + (lane & 15);
     auto la = [&](int buf) __attribute__((always_inline)) {
         return (uint32_t)(uintptr_t)(lds_ptr_t)(lds + buf * A_U + a16);
     };
-    // refill group g (0: A0 B2, 1: B0 A2, 2: B1 A1), read r of TMN; B addresses of the chunk in bq
-    auto rd = [&](int g, int r, uint32_t abase, const uint32_t (&bq)[TN]) __attribute__((always_inline)) {
-        const bool isA = g == 0 ? r < TM : r >= TN;
-        const int k = g == 0 ? (r < TM ? r : r - TM) : (r < TN ? r : r - TN);
-        const int pc = g == 0 ? (isA ? 0 : 2) : g == 1 ? (isA ? 2 : 0) : 1;
-        if (isA)
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fa[pc][k]) : "v"(abase), "i"((pc * 4 * MT + 16 * k) * 16));
-        else
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fb[pc][k]) : "v"(bq[k]), "i"(pc * WMAX * 16));
-    };
-    auto mf = [&](int t, int q) __attribute__((always_inline)) {
-        const int i = q / TN, j = q % TN;
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[PA[t]][i]),
-                                                            __builtin_bit_cast(bf16x8, fb[PB[t]][j]), acc[i][j], 0,
-                                                            0, 0);
-    };
-    auto fence_all = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(fa[pc][i]));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(fb[pc][j]));
-        }
-    };
 
     // ---- prologue: windows of the first two groups the range reads, weight stages of its first
-    // two chunks
+    // NST chunks
     const int g_first = (4 * c_begin) / TAPS;
     dma_win(g_first);
     if (g_first + 1 < cin_g) dma_win(g_first + 1);
@@ -217,104 +175,67 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_win_x6(X6Args a
     for (int st = 0; st < NST; ++st) dma_a(min(c_begin + st, c_end - 1), st);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // both windows and every stage landed everywhere
-    uint32_t bcur[TN], bnxt[TN];
+    X6BWin<TN, WMAX> bcur, bnxt;  // the lane's B addresses of chunk c / c + 1
     {
         off_all();  // chunk c_begin
 #pragma unroll
-        for (int j = 0; j < TN; ++j) bnxt[j] = bbase[j] + off_n;  // chunk 0
+        for (int j = 0; j < TN; ++j) bnxt.a[j] = bbase[j] + off_n;  // chunk 0
         off_all();  // chunk c_begin + 1, read at the first chunk's top
-        const uint32_t a0 = la(0);
-#pragma unroll
-        for (int r = 0; r < TMN; ++r) rd(0, r, a0, bnxt);
-#pragma unroll
-        for (int r = 0; r < TMN; ++r) rd(1, r, a0, bnxt);
+        f.rd_group(0, la(0), bnxt);
+        f.rd_group(1, la(0), bnxt);
     }
     // group whose last chunk comes next, and that chunk: its buffer is refilled after that barrier
     int end_g = g_first;
     int end_c = (g_first * TAPS + TAPS - 1) / 4;
     int buf = 0;  // stage of chunk c
     for (int c = c_begin; c < c_end; ++c) {
-        const int nbuf = buf + 1 == NST ? 0 : buf + 1;
+        const int nbuf = buf + 1 == NST ? 0 : buf + 1;  // a ring of NST stages
         const uint32_t a_cur = la(buf), a_nxt = la(nbuf);
         const int c2 = min(c + NST, c_end - 1);  // past the end: a harmless reload of the last chunk
 #pragma unroll
-        for (int j = 0; j < TN; ++j) bcur[j] = bnxt[j];
+        for (int j = 0; j < TN; ++j) bcur.a[j] = bnxt.a[j];
 #pragma unroll
-        for (int j = 0; j < TN; ++j) bnxt[j] = bbase[j] + off_n;  // chunk c + 1 (computed in chunk c - 1)
-        // block 0 (needs R0): R2 of this chunk interleaved
-        asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(TMN > 15 ? 15 : TMN) : "memory");
-        fence_all();
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < NB; ++q) {
-            mf(0, q);
-#pragma unroll
-            for (int r = q * TMN / NB; r < (q + 1) * TMN / NB; ++r) rd(2, r, a_cur, bcur);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // block 1 (needs R1)
-        asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(TMN > 15 ? 15 : TMN) : "memory");
-        fence_all();
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < NB; ++q) {
-            mf(1, q);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // block 2 (needs R2)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        fence_all();
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < NB; ++q) {
-            mf(2, q);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // this weight stage and every fragment of chunk c read by all; the next stage (and any
+        for (int j = 0; j < TN; ++j) bnxt.a[j] = bbase[j] + off_n;  // chunk c + 1 (computed in chunk c - 1)
+        f.head(a_cur, bcur);  // blocks 0-2 (x6_loop.h)
+        // This weight stage and every fragment of chunk c read by all; the next stage (and any
         // window DMA'd since the previous barrier) landed -- with 3 stages the A_PW DMA
-        // instructions of the chunk after it (issued last) may still be in flight.  The vmcnt is
-        // explicit: the compiler does not count LDS-DMA as LDS writes at a workgroup barrier (it
-        // emitted a bare s_barrier here), and the fragment reads are inline asm it cannot see
-        if constexpr (NST == 3)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"i"(A_PW) : "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);
+        // instructions of the chunk after it (issued last) may still be in flight
+        f.template barrier<NST == 3 ? A_PW : 0>();
         if (c == end_c) {  // group end_g is read for the last time: its buffer takes group end_g + 2
             if (end_g + 2 < cin_g) dma_win(end_g + 2);
             ++end_g;
             end_c = (end_g * TAPS + TAPS - 1) / 4;
         }
         __builtin_amdgcn_sched_barrier(0);
-        // blocks 3-5: R0 (block 3) and R1 (block 5) of the next chunk, weight DMA of chunk c2
+        // blocks 3-5: R0 (block 3) and R1 (block 5) of the next chunk, the weight DMA of chunk c2
+        // into the stage just read, chunk c + 2's offset steps in block 4
 #pragma unroll
         for (int q = 0; q < NB; ++q) {
-            mf(3, q);
+            f.mf(3, q);
             constexpr int N3 = TMN + 1;
 #pragma unroll
             for (int o = q * N3 / NB; o < (q + 1) * N3 / NB; ++o) {
-                if (o < TMN) rd(0, o, a_nxt, bnxt);
+                if (o < TMN) f.rd(0, o, a_nxt, bnxt);
                 else dma_a_unit(c2, buf, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int q = 0; q < NB; ++q) {
-            mf(4, q);
+            f.mf(4, q);
             constexpr int N4 = A_PW - 2;
 #pragma unroll
             for (int o = q * N4 / NB; o < (q + 1) * N4 / NB; ++o) dma_a_unit(c2, buf, 1 + o);
-            if (q < OFF_STEPS) off_step(q);  // chunk c + 2's offsets
+            if (q < OFF_STEPS) off_step(q);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int q = 0; q < NB; ++q) {
-            mf(5, q);
+            f.mf(5, q);
             constexpr int N5 = TMN + 1;
 #pragma unroll
             for (int o = q * N5 / NB; o < (q + 1) * N5 / NB; ++o) {
-                if (o < TMN) rd(1, o, a_nxt, bnxt);
+                if (o < TMN) f.rd(1, o, a_nxt, bnxt);
                 else dma_a_unit(c2, buf, A_PW - 1);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -322,7 +243,7 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_win_x6(X6Args a
         buf = nbuf;
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the last (unused) reads / loads landed
-    fence_all();
+    f.fence_all();
 
     // ---- epilogue: a slab of a multi-slab tile leaves an fp32 partial (folded in slab order by
     // conv_x6_fixup); a whole tile adds bias + ReLU and writes X6 / X6P slices or fp32 NCHW
@@ -335,12 +256,12 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_win_x6(X6Args a
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const int q = (wm0 + i * 16) / 4 + (lane >> 4);
-                store_slab_quad(srs, sbase + (uint32_t)(q * PT + pl) * 16u, acc[i][j]);
+                store_slab_quad(srs, sbase + (uint32_t)(q * PT + pl) * 16u, f.acc[i][j]);
             }
         }
         continue;
     }
-    const int cout8 = (G.cout + 7) & ~7;
+    const X6Out out = x6_out(G);
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int p = p0 + wp0 + j * 16 + (lane & 15);
@@ -351,71 +272,16 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_win_x6(X6Args a
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int ml = wm0 + i * 16 + 4 * (lane >> 4);  // first of 4 consecutive channels
-            const int mq = m0 + ml;
             float v[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                v[t] = acc[i][j][t] + s_bias[ml + t];
+                v[t] = f.acc[i][j][t] + s_bias[ml + t];
                 if (G.relu) v[t] = fmaxf(v[t], 0.f);
             }
-            if (G.out_f32) {
-                float* ob = static_cast<float*>(G.out) + ((size_t)n * G.out_c + G.out_off) * HW + rem;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    if (mq + t < G.cout) ob[(size_t)(mq + t) * HW] = v[t];
-            } else if (mq < cout8) {
-                const int grp = mq >> 3, half = (mq >> 2) & 1;
-                store4_x6(static_cast<uint8_t*>(G.out) + (size_t)x6_unit(G.out_l, n, grp, y, x) * 16 + half * 8,
-                          G.out_ps, v);
-                if (G.out2)
-                    store4_x6(static_cast<uint8_t*>(G.out2) + (size_t)x6_unit(G.out2_l, n, grp, y, x) * 16 + half * 8,
-                              G.out2_ps, v);
-            }
+            x6_store_quad(out, n, y, x, rem, HW, m0 + ml, v);
         }
     }
-    }  // pieces
-}
-
-// weights [cout][cin][ks][ks] (fp32, physical input channel order) -> X6 chunks in pair order:
-// chunk c, k-group gi = pair q = 4c + gi = (group q / taps, tap q % taps); pairs past the last
-// group are zero.  Same unit format as x6_pack_weights ([chunk][piece][4][Mpad][8] bf16).
-void x6_pack_weights_pairs(const float* w, int cout, int cin, int ks, int Mpad, int* nK_out,
-                           std::vector<uint16_t>& out) {
-    const int taps = ks * ks;
-    const int cin_g = (cin + 7) / 8;
-    const int nK = (cin_g * taps + 3) / 4;
-    *nK_out = nK;
-    out.assign((size_t)nK * 12 * Mpad * 8, 0);
-    auto rne = [](float x) -> uint32_t {
-        uint32_t u;
-        std::memcpy(&u, &x, 4);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return u >> 16;
-    };
-    auto f = [](uint32_t h) {
-        const uint32_t u = h << 16;
-        float x;
-        std::memcpy(&x, &u, 4);
-        return x;
-    };
-    for (int c = 0; c < nK; ++c)
-        for (int gi = 0; gi < 4; ++gi) {
-            const int q = 4 * c + gi, grp = q / taps, tap = q % taps;
-            if (grp >= cin_g) continue;
-            for (int m = 0; m < cout; ++m)
-                for (int e = 0; e < 8; ++e) {
-                    const int ch = grp * 8 + e;
-                    if (ch >= cin) continue;
-                    const float x = w[((size_t)m * cin + ch) * taps + tap];
-                    const uint32_t h0 = rne(x);
-                    const float r = x - f(h0);
-                    const uint32_t h1 = rne(r);
-                    const uint32_t h2 = rne(r - f(h1));
-                    const uint32_t hs[3] = {h0, h1, h2};
-                    for (int pc = 0; pc < 3; ++pc)
-                        out[(((size_t)c * 12 + pc * 4 + gi) * Mpad + m) * 8 + e] = (uint16_t)hs[pc];
-                }
-        }
+    }  // work units
 }
 
 // window capacities (units per (piece, group)): LDS = 3 weight stages (72 KB) + 2 x 3 x 832 units
@@ -468,7 +334,7 @@ void launch_conv_win_x6(const X6Args& a0, hipStream_t st) {
     } else {
         throw std::invalid_argument("conv_win_x6: window exceeds LDS");
     }
-    if (a.units != a.tiles) launch_conv_x6_fixup(a, 128, 256, st);
+    launch_conv_x6_fixup(a, 128, 256, st);
 }
 
 }  // namespace opose

@@ -33,9 +33,7 @@
 //    extra barrier at its start (one step in twelve).
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 #include <stdexcept>
-#include <vector>
 
 #include "common.h"
 #include "kernels.h"
@@ -100,16 +98,12 @@ __global__ __launch_bounds__(64 * NW, 1) void conv_wino_x6(X6Args a) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nM = a.Mpad / MT;
-    int id;
-    {  // XCD-contiguous tile ids (guide T1): blocks b and b + 8 share an XCD
-        const int b = blockIdx.x, Gw = gridDim.x, q = Gw >> 3, rr = Gw & 7, xcd = b & 7;
-        id = xcd * q + min(xcd, rr) + (b >> 3);
-    }
+    const int id = x6_xcd_id();
     const X6Group G = a.g[x6_group_of(a, id)];
     const int H = G.H, W = G.W, TW = (W + 1) >> 1;
     const int mt = (id - G.t0) % nM;
     const int t0 = ((id - G.t0) / nM) * TT, m0 = mt * MT;
-    if (tid < MT) s_bias[tid] = (m0 + tid < G.cout) ? G.bias[m0 + tid] : 0.f;
+    x6_load_bias(s_bias, G, m0, MT);
 
     // ---- window geometry: padded rows of the first and last real tile of the workgroup
     const int P = (int)G.in_l.rs;
@@ -189,8 +183,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv_wino_x6(X6Args a) {
         woff[u] = (uint32_t)(pg * a.Mpad + m0 + m) * 16u;
     }
     auto dma_a_unit = [&](uint32_t so, int buf, int u) __attribute__((always_inline)) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(lds + buf * A_U + (wave * A_PW + u) * 64), 16, lane16,
-                                                 (int)(so + woff[u]), 0, 0);
+        x6_dma_weights_unit(rw, (lds_units_t)(lds + buf * A_U), (wave * A_PW + u) * 64, lane16, so + woff[u]);
     };
 
     // ---- per-lane B addressing: pair q = 4c + gi of chunk c -> (group pg, kernel row pk); the
@@ -285,9 +278,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv_wino_x6(X6Args a) {
     // MFMA of A slot sl and B piece pb (set `set`) for transform v, accumulator block qq
     auto mf = [&](int v, int sl, int set, int pb, int qq) __attribute__((always_inline)) {
         const int i = qq / TN, j = qq % TN;
-        acc[v][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[sl][i]),
-                                                               __builtin_bit_cast(bf16x8, fb[set][pb][j]),
-                                                               acc[v][i][j], 0, 0, 0);
+        acc[v][i][j] = mfma_x6(fa[sl][i], fb[set][pb][j], acc[v][i][j]);
     };
     auto fence_a = [&](int sl) __attribute__((always_inline)) {
 #pragma unroll
@@ -463,7 +454,8 @@ __global__ __launch_bounds__(64 * NW, 1) void conv_wino_x6(X6Args a) {
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
-    // ---- epilogue: output transform, bias + ReLU, two pixels per tile
+    // ---- epilogue: output transform, bias + ReLU, two pixels per tile (the store is x6.h's
+    // x6_store_quad written out: through the shared function this kernel's scratch use grew)
     const int cout8 = (G.cout + 7) & ~7;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -505,49 +497,6 @@ __global__ __launch_bounds__(64 * NW, 1) void conv_wino_x6(X6Args a) {
             }
         }
     }
-}
-
-// weights [cout][cin][3][3] (fp32, physical channel order) -> U_v in pair order: step s = 4c + v,
-// k-group gi = pair q = 4c + gi = (group q / 3, kernel row q % 3); same unit format as
-// x6_pack_weights ([step][piece][4][Mpad][8] bf16)
-void x6_pack_weights_wino(const float* w, int cout, int cin, int Mpad, int* nK_out, std::vector<uint16_t>& out) {
-    const int cin_g = (cin + 7) / 8;
-    const int nK = (cin_g * 3 + 3) / 4;
-    *nK_out = nK;
-    out.assign((size_t)nK * 4 * 12 * Mpad * 8, 0);
-    auto rne = [](float x) -> uint32_t {
-        uint32_t u;
-        std::memcpy(&u, &x, 4);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return u >> 16;
-    };
-    auto f = [](uint32_t h) {
-        const uint32_t u = h << 16;
-        float x;
-        std::memcpy(&x, &u, 4);
-        return x;
-    };
-    static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    for (int c = 0; c < nK; ++c)
-        for (int v = 0; v < 4; ++v)
-            for (int gi = 0; gi < 4; ++gi) {
-                const int q = 4 * c + gi, grp = q / 3, ky = q % 3;
-                if (grp >= cin_g) continue;
-                for (int m = 0; m < cout; ++m)
-                    for (int e = 0; e < 8; ++e) {
-                        const int ch = grp * 8 + e;
-                        if (ch >= cin) continue;
-                        const float* wr = w + (((size_t)m * cin + ch) * 3 + ky) * 3;
-                        const float x = (float)(Gm[v][0] * (double)wr[0] + Gm[v][1] * (double)wr[1] + Gm[v][2] * (double)wr[2]);
-                        const uint32_t h0 = rne(x);
-                        const float r = x - f(h0);
-                        const uint32_t h1 = rne(r);
-                        const uint32_t h2 = rne(r - f(h1));
-                        const uint32_t hs[3] = {h0, h1, h2};
-                        for (int pc = 0; pc < 3; ++pc)
-                            out[((((size_t)(4 * c + v) * 3 + pc) * 4 + gi) * Mpad + m) * 8 + e] = (uint16_t)hs[pc];
-                    }
-            }
 }
 
 // window units of a tile block, and the whole launch's worst case: tiles numbered across frames

@@ -18,26 +18,27 @@
 //   by buffer loads to LDS, the im2col pixels of a (piece, channel group, tap) by
 //   buffer_load_dwordx4 ... lds with the zero padding from the buffer range check.
 // * K chunk = 32 k = 4 channel groups of one tap (or 4 taps of a single group when Cin <= 8),
-//   two LDS stages, one barrier per chunk.  Work units (tile, k slab): a tile of a group with
+//   two LDS stages (weights + im2col tile each), one barrier per chunk: the six-block schedule
+//   that x6_loop.h describes and conv_win_x6 also runs.  Work units (tile, k slab): a tile of a group with
 //   `slabs` slabs sums fixed chunk ranges, each from zero, and conv_x6_fixup folds the slab
 //   partials in slab order (common.h X6Group::slabs, x6.h x6_unit_of).
 // * The epilogue adds bias, applies ReLU and writes the output split again (X6) into a
-//   group slice of a wider buffer (the CPM concat), or fp32 NCHW for the network outputs.
+//   group slice of a wider buffer (the CPM concat), or fp32 NCHW for the network outputs
+//   (x6.h x6_store_quad); the pooled launch takes the 2x2 max first.
+// Also here: the slab fixup, the X6 <-> fp32 converters and X6P padding kernels, conv1_1
+// (direct fp32) and the windowed conv1_2 + pool.  The weight packers are in x6_pack.cpp.
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 #include <stdexcept>
-#include <vector>
 
 #include "common.h"
 #include "kernels.h"
-#include "x6.h"
+#include "x6_loop.h"
 
 namespace opose {
 
-
-// Main loop: v_mfma_f32_16x16x32_bf16, one k-step (32 k) per chunk, refill-after-last-use
-// fragment schedule pinned by sched_barrier (see below).  Measured and dropped:
+// Main loop: v_mfma_f32_16x16x32_bf16, one k-step (32 k) per chunk, the refill-after-last-use
+// fragment schedule of x6_loop.h pinned by sched_barrier.  Measured and dropped:
 // a two-wait loop, the 32x32x16 pipelined loop, and im2col fragments loaded straight into
 // registers (same speed, LDS for the weights only).
 template <int MT, int PT, bool SMALL, int KS>
@@ -47,10 +48,7 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_x6(X6Args a) {
     // waves along M: 8-wave tiles one per 64 rows; the 4-wave tiles 2 x 2
     constexpr int NW = x6_waves(MT, PT), NWM = NW == 8 ? MT / 64 : 2, NWP = NW / NWM;
     constexpr int WM = MT / NWM, WP = PT / NWP;
-    constexpr int MB = 16;                       // MFMA block (rows = pixels)
-    constexpr int TM = WM / MB, TN = WP / MB;
-    constexpr int ACC_N = MB * MB / 64;          // accumulator registers per block
-    using AccT = f32x4;
+    constexpr int TM = WM / 16, TN = WP / 16;    // 16 x 16 MFMA blocks of a wave
     constexpr int PJ = PT / 64;                  // 64-pixel runs per tile
     constexpr int A_U = 12 * MT, B_U = 12 * PT;  // 16-byte units per stage
     constexpr int A_PW = A_U / 64 / NW;          // A DMA instructions per wave per chunk
@@ -88,11 +86,7 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_x6(X6Args a) {
     const int jw = wave % PJ;    // this wave's pixel run for the im2col DMA
     const int pg0 = wave / PJ;   // its first (piece, group) row; then every WPJ-th
 
-    const int Gw = gridDim.x;
-    const int b = blockIdx.x;
-    const int q = Gw >> 3, rr = Gw & 7, xcd = b & 7;
-    const int id = xcd * q + min(xcd, rr) + (b >> 3);
-    const X6Work wk = x6_work_of(a, id);
+    const X6Work wk = x6_work_of(a, x6_xcd_id());
 
     for (int k = wk.k0; k < wk.k1; ++k) {
         const int uid = wk.list ? wk.list[k] : k;
@@ -113,7 +107,7 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_x6(X6Args a) {
         const int m0 = mt * MT;
 
         __syncthreads();
-        if (tid < MT) s_bias[tid] = (m0 + tid < G.cout) ? G.bias[m0 + tid] : 0.f;
+        x6_load_bias(s_bias, G, m0, MT);
 
         // the lane's im2col pixel (run jw): byte offset of its unit in group 0, plane 0
         // (a row band's view starts its buffer resource 3 rows + 3 units early, so the halo
@@ -133,13 +127,11 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_x6(X6Args a) {
             pbase = (n * G.in_l.fs + (uint32_t)y * G.in_l.rs + (uint32_t)px + hshift) * 16u;
         }
 
-        AccT acc[TM][TN];
+        f32x4 acc[TM][TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < ACC_N; ++r) acc[i][j][r] = 0.f;
+            for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
         auto tap_off = [&](int tap) __attribute__((always_inline)) -> uint32_t {
             const int ky = tap / ks;
@@ -188,37 +180,28 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_x6(X6Args a) {
 #pragma unroll
             for (int u = 0; u < B_PW; ++u) dma_b_unit(c, bp, buf, u);
         };
-        // weights: one buffer resource per chunk, the unit's row offset in soffset, lane * 16 in voffset
+        // weights: run u of this wave's A_PW (x6.h x6_dma_weights_unit), its row offset in soffset
         const uint32_t lane16 = (uint32_t)lane * 16u;
         auto dma_a_unit = [&](int c, int buf, int u) __attribute__((always_inline)) {
-            uint4* As = lds + buf * STAGE_U;
             const int unit0 = (wave * A_PW + u) * 64;
             const int pg = unit0 / MT, m = unit0 - pg * MT;
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)(G.wt + (size_t)c * 12 * a.Mpad * 16), (short)0, (int)0x7fffffff, 0x00020000);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(As + unit0), 16, lane16,
-                                                     (int)((uint32_t)(pg * a.Mpad + m0 + m) * 16u), 0, 0);
+            x6_dma_weights_unit(x6_weights_rsrc(G.wt, a.Mpad, c), (lds_units_t)(lds + buf * STAGE_U), unit0, lane16,
+                                (uint32_t)(pg * a.Mpad + m0 + m) * 16u);
         };
         auto dma_a = [&](int c, int buf) __attribute__((always_inline)) {
 #pragma unroll
             for (int u = 0; u < A_PW; ++u) dma_a_unit(c, buf, u);
         };
 
-        i32x4 fa[1][3][TM], fb[1][3][TN];
+        i32x4 fa[3][TM], fb[3][TN];
         {
-            // 16x16x32 MFMAs: a chunk (32 k) is one k-step.  Lane l holds row / pixel (l & 15) and
-            // the k-group (l >> 4) of its 16-row block; the LDS layout is the same [piece][group][row]
-            // unit array (ds_read_b128's 16-lane phases hit 4 rows of each of 4 groups: conflict free).
-            // One fragment set: the 6 piece products run as blocks of TM*TN MFMAs in the order
-            //   (0,2) (0,0) (0,1) | barrier | (1,0) (2,0) (1,1)
-            // and each piece's registers are refilled with the next chunk's fragments right after
-            // their last use in this chunk: R0 = A0, B2 (after block 2), R1 = B0, A2 (after block 4),
-            // R2 = B1, A1 (in the next chunk's block 0).  The barrier sits after block 2: by then
-            // every wave has read this chunk's stage (R2 waited before block 2) and the next stage
-            // has landed (vmcnt(0)), so the next chunk's R0 / R1 reads and the DMA of the chunk
-            // after it (into this stage) follow it, interleaved one per MFMA gap.
-            constexpr int PA[6] = {0, 0, 0, 1, 2, 1};
-            constexpr int PB[6] = {2, 0, 1, 0, 0, 1};
+            // The six-block chunk schedule described in x6_loop.h (fragment set, refill groups R0-R2,
+            // waits, barrier after block 2), written out here: conv_win_x6 runs it through
+            // X6Frags, but with the fragments in that holder this kernel's generated code changed
+            // beyond register names (other s_waitcnt counts in the epilogue), so it keeps its own
+            // copy.  A change to the schedule is made in x6_loop.h and here.  Own to this kernel:
+            // B fragments from one base plus an immediate, two stages (vmcnt(0) at the barrier),
+            // and the A + B DMA of chunk c + 2 spread over blocks 3-5.
             constexpr int NB = TM * TN;           // MFMAs per block
             constexpr int TMN = TM + TN;          // reads per refill group
             constexpr int NDA = A_PW + B_PW;      // LDS-DMA instructions per chunk
@@ -237,26 +220,24 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_x6(X6Args a) {
                 const int pc = g == 0 ? (isA ? 0 : 2) : g == 1 ? (isA ? 2 : 0) : 1;
                 if (isA)
                     asm volatile("ds_read_b128 %0, %1 offset:%2"
-                                 : "=v"(fa[0][pc][k])
+                                 : "=v"(fa[pc][k])
                                  : "v"(abase), "i"((pc * 4 * MT + 16 * k) * 16));
                 else
                     asm volatile("ds_read_b128 %0, %1 offset:%2"
-                                 : "=v"(fb[0][pc][k])
+                                 : "=v"(fb[pc][k])
                                  : "v"(bbase), "i"((pc * 4 * PT + 16 * k) * 16));
             };
             auto mf = [&](int t, int q) __attribute__((always_inline)) {
                 const int i = q / TN, j = q % TN;
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[0][PA[t]][i]),
-                                                                    __builtin_bit_cast(bf16x8, fb[0][PB[t]][j]),
-                                                                    acc[i][j], 0, 0, 0);
+                acc[i][j] = mfma_x6(fa[kPieceA[t]][i], fb[kPieceB[t]][j], acc[i][j]);
             };
             auto fence_all = [&]() __attribute__((always_inline)) {
 #pragma unroll
                 for (int pc = 0; pc < 3; ++pc) {
 #pragma unroll
-                    for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(fa[0][pc][i]));
+                    for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(fa[pc][i]));
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(fb[0][pc][j]));
+                    for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(fb[pc][j]));
                 }
             };
             dma_a(c_begin, 0);
@@ -308,8 +289,8 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_x6(X6Args a) {
                     mf(2, q);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                // this stage read by all; the next stage landed (explicit vmcnt(0): the compiler's
-                // barrier fence does not reliably count LDS-DMA, see conv_win.hip)
+                // this stage read by all; the next stage landed (the vmcnt is explicit: x6_loop.h
+                // X6Frags::barrier says why)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 __builtin_amdgcn_sched_barrier(0);
@@ -354,27 +335,22 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_x6(X6Args a) {
             fence_all();
         }
 
-        // ---- epilogue
-        // accumulator register r of block (i, j): rows (channels) ml0 + (r & 3) of quad r >> 2,
-        // column (pixel) pl.  32x32: quad qd covers rows 32i + 8qd + 4hk .. +3, pixel 32j + l31;
-        // 16x16: rows 16i + 4(l >> 4) .. +3, pixel 16j + (l & 15).
+        // ---- epilogue: lane l holds in acc[i][j] rows (channels) 16i + 4(l >> 4) .. +3 of the
+        // wave's rows, column (pixel) 16j + (l & 15)
         const bool whole = un.whole;
-        const int cout8 = (G.cout + 7) & ~7;
+        const X6Out out = x6_out(G);
+        const int cout8 = out.cout8;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int pl = wp0 + j * 16 + (lane & 15);
             const int p = p0 + pl;
-            auto quad_row = [&](int i, int qd) __attribute__((always_inline)) {
-                (void)qd;
-                return wm0 + i * 16 + 4 * (lane >> 4);
-            };
+            auto quad_row = [&](int i) __attribute__((always_inline)) { return wm0 + i * 16 + 4 * (lane >> 4); };
             if (!whole) {
-                static_assert(ACC_N == 4, "slab quads: one 16x16 accumulator block per lane quad");
                 const __amdgpu_buffer_rsrc_t srs = slab_rsrc(a.partial);
                 const uint32_t sbase = (uint32_t)uid * (uint32_t)(MT * PT * 4);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
-                    store_slab_quad(srs, sbase + (uint32_t)((quad_row(i, 0) / 4) * PT + pl) * 16u, acc[i][j]);
+                    store_slab_quad(srs, sbase + (uint32_t)((quad_row(i) / 4) * PT + pl) * 16u, acc[i][j]);
                 continue;
             }
             if (a.pool) {
@@ -387,26 +363,19 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_x6(X6Args a) {
                 const int yo = remo / Wo, xo = remo - yo * Wo;
                 const bool lead = (lane & 3) == 0 && p < npix;
 #pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int qd = 0; qd < ACC_N / 4; ++qd) {
-                        const int ml = quad_row(i, qd);
+                for (int i = 0; i < TM; ++i) {
+                        const int ml = quad_row(i);
                         const int mq = m0 + ml;
                         float v[4];
 #pragma unroll
                         for (int t = 0; t < 4; ++t) {
-                            float m = acc[i][j][4 * qd + t];
+                            float m = acc[i][j][t];
                             m = fmaxf(m, __shfl_xor(m, 1));
                             m = fmaxf(m, __shfl_xor(m, 2));
                             v[t] = m + s_bias[ml + t];
                             if (G.relu) v[t] = fmaxf(v[t], 0.f);
                         }
-                        if (lead && mq < cout8) {
-                            const int grp = mq >> 3, half = (mq >> 2) & 1;
-                            store4_x6(static_cast<uint8_t*>(G.out) + (size_t)x6_unit(G.out_l, n, grp, yo, xo) * 16 +
-                                          half * 8,
-                                      G.out_ps, v);
-                        }
+                        if (lead && mq < cout8) x6_store_slice(G.out, G.out_l, G.out_ps, n, yo, xo, mq, v);
                     }
                 continue;
             }
@@ -415,51 +384,18 @@ __global__ __launch_bounds__(64 * x6_waves(MT, PT), 1) void conv_x6(X6Args a) {
             const int rem = p - n * HW;
             const int y = rem / W, x = rem - y * W;
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int qd = 0; qd < ACC_N / 4; ++qd) {
-                    const int ml = quad_row(i, qd);  // first of 4 consecutive channels (half a group)
+            for (int i = 0; i < TM; ++i) {
+                    const int ml = quad_row(i);  // first of 4 consecutive channels (half a group)
                     const int mq = m0 + ml;
                     float v[4];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
-                        v[t] = acc[i][j][4 * qd + t] + s_bias[ml + t];
+                        v[t] = acc[i][j][t] + s_bias[ml + t];
                         if (G.relu) v[t] = fmaxf(v[t], 0.f);
                     }
-                    if (G.out_f32) {
-                        float* ob = static_cast<float*>(G.out) + ((size_t)n * G.out_c + G.out_off) * HW + rem;
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            const int m = mq + t;
-                            if (m < G.cout) ob[(size_t)m * HW] = v[t];
-                        }
-                    } else if (mq < cout8) {
-                        const int grp = mq >> 3, half = (mq >> 2) & 1;
-                        store4_x6(static_cast<uint8_t*>(G.out) + (size_t)x6_unit(G.out_l, n, grp, y, x) * 16 + half * 8,
-                                  G.out_ps, v);
-                        if (G.out2)
-                            store4_x6(static_cast<uint8_t*>(G.out2) + (size_t)x6_unit(G.out2_l, n, grp, y, x) * 16 +
-                                          half * 8,
-                                      G.out2_ps, v);
-                    }
+                    x6_store_quad(out, n, y, x, rem, HW, mq, v);
                 }
         }
-    }
-}
-
-// whole X6 unit (8 channels of one pixel): three 16-byte piece stores
-__device__ __forceinline__ void store8_x6(uint8_t* unit, uint32_t ps, const float (&v)[8]) {
-    uint32_t h[3][8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) split3(v[t], h[0][t], h[1][t], h[2][t]);
-#pragma unroll
-    for (int pc = 0; pc < 3; ++pc) {
-        uint4 w;
-        w.x = h[pc][0] | (h[pc][1] << 16);
-        w.y = h[pc][2] | (h[pc][3] << 16);
-        w.z = h[pc][4] | (h[pc][5] << 16);
-        w.w = h[pc][6] | (h[pc][7] << 16);
-        *reinterpret_cast<uint4*>(unit + (size_t)pc * ps) = w;
     }
 }
 
@@ -543,7 +479,7 @@ __global__ __launch_bounds__(256) void conv_x6_fixup(X6Args a) {
         const int Wo = G.W / 2, HWo = (G.H / 2) * Wo;
         const int q = p >> 2, n = q / HWo, remo = q - n * HWo;
         const int yo = remo / Wo, xo = remo - yo * Wo;
-        store8_x6(static_cast<uint8_t*>(G.out) + (size_t)x6_unit(G.out_l, n, mg >> 3, yo, xo) * 16, G.out_ps, v);
+        x6_store_slice(G.out, G.out_l, G.out_ps, n, yo, xo, mg, v);
         return;
     }
     fold(pl, v);
@@ -555,17 +491,8 @@ __global__ __launch_bounds__(256) void conv_x6_fixup(X6Args a) {
     }
     const int n = p / HW;
     const int rem = p - n * HW;
-    if (G.out_f32) {
-        float* ob = static_cast<float*>(G.out) + ((size_t)n * G.out_c + G.out_off) * HW + rem;
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-            if (mg + t < G.cout) ob[(size_t)(mg + t) * HW] = v[t];
-        return;
-    }
-    const int grp = mg >> 3;
     const int y = rem / G.W, x = rem - y * G.W;
-    store8_x6(static_cast<uint8_t*>(G.out) + (size_t)x6_unit(G.out_l, n, grp, y, x) * 16, G.out_ps, v);
-    if (G.out2) store8_x6(static_cast<uint8_t*>(G.out2) + (size_t)x6_unit(G.out2_l, n, grp, y, x) * 16, G.out2_ps, v);
+    x6_store_quad(x6_out(G), n, y, x, rem, HW, mg, v);
 }
 
 static int grid_for(size_t total) {
@@ -660,23 +587,13 @@ __global__ __launch_bounds__(256) void to_x6_kernel(const float* __restrict__ in
         const size_t t = e / HW;
         const int gq = (int)(t % G8);
         const int n = (int)(t / G8);
-        uint32_t h[3][8];
+        float v[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int c = gq * 8 + k;
-            const float x = c < C ? in[((size_t)n * cstride + coff + c) * HW + pix] : 0.f;
-            split3(x, h[0][k], h[1][k], h[2][k]);
+            v[k] = c < C ? in[((size_t)n * cstride + coff + c) * HW + pix] : 0.f;
         }
-        uint8_t* o = out + ((size_t)(n * cg + goff + gq) * HW + pix) * 16;
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc) {
-            uint4 w;
-            w.x = h[pc][0] | (h[pc][1] << 16);
-            w.y = h[pc][2] | (h[pc][3] << 16);
-            w.z = h[pc][4] | (h[pc][5] << 16);
-            w.w = h[pc][6] | (h[pc][7] << 16);
-            *reinterpret_cast<uint4*>(o + (size_t)pc * ps) = w;
-        }
+        store8_x6(out + ((size_t)(n * cg + goff + gq) * HW + pix) * 16, ps, v);
     }
 }
 
@@ -736,69 +653,11 @@ __global__ __launch_bounds__(256) void maxpool_x6_kernel(const uint8_t* __restri
                 m[k] = d == 0 ? v : fmaxf(m[k], v);
             }
         }
-        uint32_t h[3][8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) split3(m[k], h[0][k], h[1][k], h[2][k]);
-        uint8_t* o = out + e * 16;
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc) {
-            uint4 w;
-            w.x = h[pc][0] | (h[pc][1] << 16);
-            w.y = h[pc][2] | (h[pc][3] << 16);
-            w.z = h[pc][4] | (h[pc][5] << 16);
-            w.w = h[pc][6] | (h[pc][7] << 16);
-            *reinterpret_cast<uint4*>(o + (size_t)pc * ops) = w;
-        }
+        store8_x6(out + e * 16, ops, m);
     }
 }
 
 // ------------------------------------------------------------------ host side
-// weights [cout][cin][ks][ks] (fp32, physical input channel order) -> X6 chunks
-void x6_pack_weights(const float* w, int cout, int cin, int ks, int Mpad, int* nK_out, std::vector<uint16_t>& out) {
-    const int taps = ks * ks;
-    const int cin_g = (cin + 7) / 8;
-    const bool small = cin_g == 1;
-    const int nK = small ? (taps + 3) / 4 : ((cin_g + 3) / 4) * taps;
-    *nK_out = nK;
-    out.assign((size_t)nK * 12 * Mpad * 8, 0);
-    auto rne = [](float x) -> uint32_t {
-        uint32_t u;
-        std::memcpy(&u, &x, 4);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return u >> 16;
-    };
-    auto f = [](uint32_t h) {
-        const uint32_t u = h << 16;
-        float x;
-        std::memcpy(&x, &u, 4);
-        return x;
-    };
-    for (int c = 0; c < nK; ++c)
-        for (int gi = 0; gi < 4; ++gi) {
-            int tap, grp;
-            if (small) {
-                tap = c * 4 + gi;
-                grp = 0;
-            } else {
-                tap = c % taps;
-                grp = (c / taps) * 4 + gi;
-            }
-            for (int m = 0; m < cout; ++m)
-                for (int e = 0; e < 8; ++e) {
-                    const int ch = grp * 8 + e;
-                    if (tap >= taps || ch >= cin) continue;
-                    const float x = w[((size_t)m * cin + ch) * taps + tap];
-                    const uint32_t h0 = rne(x);
-                    const float r = x - f(h0);
-                    const uint32_t h1 = rne(r);
-                    const uint32_t h2 = rne(r - f(h1));
-                    const uint32_t hs[3] = {h0, h1, h2};
-                    for (int pc = 0; pc < 3; ++pc)
-                        out[(((size_t)c * 12 + pc * 4 + gi) * Mpad + m) * 8 + e] = (uint16_t)hs[pc];
-                }
-        }
-}
-
 // number the groups' tiles and work units (X6Group::t0 / u0, X6Args::tiles / units) for an
 // MT x PT tile; slabs 0 counts as 1
 X6Args x6_number_tiles(const X6Args& a0, int mt, int pt) {
@@ -821,6 +680,13 @@ X6Args x6_number_tiles(const X6Args& a0, int mt, int pt) {
     return a;
 }
 
+// a numbered launch's slab fixup, when any of its tiles has more than one slab
+template <int MT, int PT>
+static void launch_fixup_tile(const X6Args& a, hipStream_t st) {
+    if (a.units != a.tiles)
+        hipLaunchKernelGGL((conv_x6_fixup<MT, PT>), dim3(a.tiles, MT * PT / 8 / 256), dim3(256), 0, st, a);
+}
+
 template <int MT, int PT>
 static void launch_x6_tile(const X6Args& a0, hipStream_t st) {
     const X6Args a = x6_number_tiles(a0, MT, PT);
@@ -837,13 +703,12 @@ static void launch_x6_tile(const X6Args& a0, hipStream_t st) {
         hipLaunchKernelGGL((conv_x6<MT, PT, false, 1>), dim3(a.sk_grid), blk, 0, st, a);
     else
         hipLaunchKernelGGL((conv_x6<MT, PT, false, 0>), dim3(a.sk_grid), blk, 0, st, a);
-    if (a.units != a.tiles)
-        hipLaunchKernelGGL((conv_x6_fixup<MT, PT>), dim3(a.tiles, MT * PT / 8 / 256), dim3(256), 0, st, a);
+    launch_fixup_tile<MT, PT>(a, st);
 }
 
 void launch_conv_x6_fixup(const X6Args& a, int mt, int pt, hipStream_t st) {
     if (mt != 128 || pt != 256) throw std::invalid_argument("conv_x6_fixup: tile");
-    hipLaunchKernelGGL((conv_x6_fixup<128, 256>), dim3(a.tiles, 128 * 256 / 8 / 256), dim3(256), 0, st, a);
+    launch_fixup_tile<128, 256>(a, st);
 }
 
 void launch_conv_x6(const X6Args& a, int mt, int pt, hipStream_t st) {
@@ -945,18 +810,7 @@ __global__ __launch_bounds__(256) void conv_first_x6_kernel(Conv1Segs S, const f
                 u[1] = make_float4(v[4], v[5], v[6], v[7]);
                 continue;
             }
-            uint32_t hp[3][8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) split3(v[k], hp[0][k], hp[1][k], hp[2][k]);
-#pragma unroll
-            for (int pc = 0; pc < 3; ++pc) {
-                uint4 w4;
-                w4.x = hp[pc][0] | (hp[pc][1] << 16);
-                w4.y = hp[pc][2] | (hp[pc][3] << 16);
-                w4.z = hp[pc][4] | (hp[pc][5] << 16);
-                w4.w = hp[pc][6] | (hp[pc][7] << 16);
-                *reinterpret_cast<uint4*>(o + (size_t)g * HW * 16 + (size_t)pc * ops) = w4;
-            }
+            store8_x6(o + (size_t)g * HW * 16, ops, v);
         }
     }
 }
@@ -1032,12 +886,7 @@ __global__ __launch_bounds__(256, 2) void conv3_pool_win_x6_kernel(Conv1Segs S, 
     __shared__ WinSmem sm;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int t;
-    {
-        const int Gw = gridDim.x, b = blockIdx.x;
-        const int q = Gw >> 3, rr = Gw & 7, xcd = b & 7;
-        t = xcd * q + min(xcd, rr) + (b >> 3);  // XCD-contiguous tiles (guide T1)
-    }
+    int t = x6_xcd_id();
     const int sk = conv1_seg_of(S, t);  // the tile's segment (a pyramid scale)
     const uint8_t* __restrict__ in = static_cast<const uint8_t*>(S.s[sk].in);
     uint8_t* __restrict__ out = S.s[sk].out;
@@ -1098,19 +947,12 @@ __global__ __launch_bounds__(256, 2) void conv3_pool_win_x6_kernel(Conv1Segs S, 
     auto store_slot = [&](int k, const f32x4& a, const f32x4& b) __attribute__((always_inline)) {
         const int u = tid + 256 * k;
         if (u >= V_PP) return;
-        uint32_t hp[3][8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            split3(a[e], hp[0][e], hp[1][e], hp[2][e]);
-            split3(b[e], hp[0][4 + e], hp[1][4 + e], hp[2][4 + e]);
-        }
+        const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+        uint4 w[3];
+        pack_pieces8(v, w);
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) {
-            i32x4 w4;
-            w4[0] = (int)(hp[pc][0] | (hp[pc][1] << 16));
-            w4[1] = (int)(hp[pc][2] | (hp[pc][3] << 16));
-            w4[2] = (int)(hp[pc][4] | (hp[pc][5] << 16));
-            w4[3] = (int)(hp[pc][6] | (hp[pc][7] << 16));
+            const i32x4 w4 = {(int)w[pc].x, (int)w[pc].y, (int)w[pc].z, (int)w[pc].w};
             // the window is only read by inline-asm ds_reads the compiler cannot see, so it is
             // written by asm too (waited for with an explicit lgkmcnt before the barrier that
             // publishes it)
@@ -1129,8 +971,7 @@ __global__ __launch_bounds__(256, 2) void conv3_pool_win_x6_kernel(Conv1Segs S, 
             (void*)(wt + (size_t)c * 12 * 64 * 16), (short)0, (int)0x7fffffff, 0x00020000);
 #pragma unroll
         for (int row = wave; row < 12; row += V_NW)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(sm.a[st] + row * 64), 16,
-                                                     (uint32_t)lane * 16u, row * 64 * 16, 0, 0);
+            x6_dma_weights_unit(rsrc, (lds_units_t)sm.a[st], row * 64, (uint32_t)lane * 16u, row * 64 * 16);
     };
     if constexpr (F32IN) {
         load_win32(0);
@@ -1146,8 +987,6 @@ __global__ __launch_bounds__(256, 2) void conv3_pool_win_x6_kernel(Conv1Segs S, 
     const int q = lane & 15, gi = lane >> 4;
     const int d = q & 3;
     const int ty = 2 * wave + (d >> 1);
-    constexpr int PA[6] = {0, 0, 0, 1, 2, 1};
-    constexpr int PB[6] = {2, 0, 1, 0, 0, 1};
     f32x4 acc[2][4];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
@@ -1192,9 +1031,7 @@ __global__ __launch_bounds__(256, 2) void conv3_pool_win_x6_kernel(Conv1Segs S, 
             for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb)
-                    acc[nb][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        __builtin_bit_cast(bf16x8, fa[set][mb][PA[tt]]), __builtin_bit_cast(bf16x8, fb[set][nb][PB[tt]]),
-                        acc[nb][mb], 0, 0, 0);
+                    acc[nb][mb] = mfma_x6(fa[set][mb][kPieceA[tt]], fb[set][nb][kPieceB[tt]], acc[nb][mb]);
         __builtin_amdgcn_sched_barrier(0);
     };
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // window block 0, weight chunks 0 and 1

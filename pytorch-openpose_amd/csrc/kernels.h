@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "common.h"
+#include "x6_pack.h"
 
 namespace opose {
 
@@ -33,13 +34,13 @@ void launch_conv(const ConvArgs& a, const int* ktab, int mt, int pt, hipStream_t
 void launch_fill_hash(float* p, size_t n, uint32_t seed, hipStream_t st);
 void launch_maxpool(const float* in, float* out, int NC, int H, int W, hipStream_t st);
 
-// conv_x6.hip (split-bf16 fp32-accurate convolution, X6 activation format: common.h)
-void x6_pack_weights(const float* w, int cout, int cin, int ks, int Mpad, int* nK_out, std::vector<uint16_t>& out);
+// conv_x6.hip (split-bf16 fp32-accurate convolution, X6 activation format: common.h; the weight
+// packers x6_pack_weights / _pairs / _wino: x6_pack.h)
 void launch_conv_x6(const X6Args& a, int mt, int pt, hipStream_t st);
 // X6Args with the groups' tiles and work units numbered for an mt x pt tile (X6Group::t0 / u0,
 // X6Args::tiles / units)
 X6Args x6_number_tiles(const X6Args& a, int mt, int pt);
-// slab fixup of a 128 x 256 tile grid (conv_win_x6)
+// slab fixup of a numbered 128 x 256 tile grid (conv_win_x6); nothing when every tile is whole
 void launch_conv_x6_fixup(const X6Args& a, int mt, int pt, hipStream_t st);
 void launch_to_x6(const float* in, int cstride, int coff, int C, int N, int HW, uint8_t* out, int cg, int goff,
                   uint32_t ps, hipStream_t st);
@@ -81,8 +82,6 @@ void launch_conv3_pool_win_x6(const uint8_t* in, uint32_t ips, int N, int H, int
 void launch_conv1x1_chain_x6(const X6ChainArgs& a, hipStream_t st);
 // conv_win.hip: the 7x7 / 3x3 convs with the im2col operand from an LDS window of the padded X6P
 // input (pair-order weights: x6_pack_weights_pairs); 128 x 256 tiles, work units (tile, k slab)
-void x6_pack_weights_pairs(const float* w, int cout, int cin, int ks, int Mpad, int* nK_out,
-                           std::vector<uint16_t>& out);
 // the windows of an N x H x W batch's tiles fit the LDS
 bool conv_win_fits(int N, int H, int W, int ks);
 // the window of any 256-pixel run of one frame W columns wide fits the LDS (whatever the height)
@@ -90,7 +89,6 @@ bool conv_win_fits_rows(int W, int ks);
 void launch_conv_win_x6(const X6Args& a, hipStream_t st);
 // Winograd F(2,3) along x for 3x3 layers on X6P inputs (conv_wino.hip): weights U_v in pair order,
 // tile slots per frame of a batch (-1: the window does not fit), whole-tile launch
-void x6_pack_weights_wino(const float* w, int cout, int cin, int Mpad, int* nK_out, std::vector<uint16_t>& out);
 int wino_tpf(int N, int H, int W);
 void launch_conv_wino_x6(const X6Args& a, hipStream_t st);
 // imgproc.hip
