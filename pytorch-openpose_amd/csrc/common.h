@@ -21,6 +21,14 @@ struct HipError : std::runtime_error {
                                     " (" + __FILE__ + ":" + std::to_string(__LINE__) + ")"); \
     } while (0)
 
+// XCD-contiguous workgroup id (guide T1) of block b in a 1-D grid of `total`: blocks b and b + 8
+// share an XCD, so XCD x takes the ids [x total / 8, (x + 1) total / 8) and neighbouring tiles
+// share its L2
+__device__ __forceinline__ int xcd_contiguous_id(int total, int b) {
+    const int q = total >> 3, rr = total & 7, xcd = b & 7;
+    return xcd * q + min(xcd, rr) + (b >> 3);
+}
+
 // ---------------------------------------------------------------- convolution
 // One "group" = one independent conv sharing the launch's shape (two CPM branches).
 struct ConvGroup {
@@ -146,6 +154,10 @@ struct X6ChainArgs {
 };
 
 // ---------------------------------------------------------------- body records
+// largest capacities opose_set_capacity accepts: peaks_finalize stages a part's peaks in LDS
+// (kMaxPeaksPerPart ints) and assemble_people's LDS is sized from both (launch_assemble)
+constexpr int kMaxPeaksPerPart = 1024, kMaxPeople = 256;
+
 struct RecordLayout {
     int peaks_per_part;  // capacity per part
     int max_people;      // subset rows

@@ -80,9 +80,7 @@ __global__ __launch_bounds__(64 * wg_waves(MT, PT), 8 / wg_waves(MT, PT)) void c
     // tiles sharing im2col halo rows or a pixel tile's M-tiles share an L2.  A tile split over
     // several workgroups leaves float32 partials that conv_sk_fixup sums in k order.
     const int Gw = gridDim.x;
-    const int b = blockIdx.x;
-    const int q = Gw >> 3, rr = Gw & 7, xcd = b & 7;
-    const int id = xcd * q + min(xcd, rr) + (b >> 3);
+    const int id = xcd_contiguous_id(Gw, blockIdx.x);
     const long long I = (long long)nM * nP * a.ngroups * nK;
     const long long lo = (long long)id * I / Gw, hi = (long long)(id + 1) * I / Gw;
 

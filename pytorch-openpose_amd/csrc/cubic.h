@@ -73,7 +73,16 @@ __device__ __forceinline__ CubicTap cubic_tap_any(int d, double scale, int ssize
     return torch ? cubic_tap_torch(d, (float)scale, ssize) : cubic_tap(d, scale, ssize);
 }
 
-// float32 image: horizontal then vertical pass, ((p0+p1)+p2)+p3 each.
+// one pass of the resize over four taps: ((p0*c0 + p1*c1) + p2*c2) + p3*c3, a rounding per operation
+__device__ __forceinline__ float cubic_dot4(float p0, float p1, float p2, float p3, const float* c) {
+    float v = p0 * c[0];
+    v = v + p1 * c[1];
+    v = v + p2 * c[2];
+    v = v + p3 * c[3];
+    return v;
+}
+
+// float32 image: horizontal then vertical pass, one cubic_dot4 each.
 // plane: row-major [rows][ld] (ld = row stride in floats)
 __device__ __forceinline__ float cubic_sample_f32(const float* __restrict__ plane, int ld, const CubicTap& ty,
                                                   const CubicTap& tx) {
@@ -81,17 +90,9 @@ __device__ __forceinline__ float cubic_sample_f32(const float* __restrict__ plan
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const float* row = plane + (size_t)ty.i[r] * ld;
-        float v = row[tx.i[0]] * tx.c[0];
-        v = v + row[tx.i[1]] * tx.c[1];
-        v = v + row[tx.i[2]] * tx.c[2];
-        v = v + row[tx.i[3]] * tx.c[3];
-        h[r] = v;
+        h[r] = cubic_dot4(row[tx.i[0]], row[tx.i[1]], row[tx.i[2]], row[tx.i[3]], tx.c);
     }
-    float o = h[0] * ty.c[0];
-    o = o + h[1] * ty.c[1];
-    o = o + h[2] * ty.c[2];
-    o = o + h[3] * ty.c[3];
-    return o;
+    return cubic_dot4(h[0], h[1], h[2], h[3], ty.c);
 }
 
 __device__ __forceinline__ int coef_short(float c) {

@@ -288,7 +288,7 @@ int opose_synchronize(opose_t* h) {
 }
 
 int opose_set_capacity(opose_t* h, int ppp, int maxp) {
-    if (!h || ppp < 1 || maxp < 1 || ppp > 1024 || maxp > 256) return OPOSE_E_ARG;
+    if (!h || ppp < 1 || maxp < 1 || ppp > kMaxPeaksPerPart || maxp > kMaxPeople) return OPOSE_E_ARG;
     if (opose_flush(h) != OPOSE_OK) return OPOSE_E_HIP;
     h->ppp = ppp;
     h->maxp = maxp;

@@ -43,6 +43,45 @@ ScaleGeom geom_from_pads(int hl, int wl, int pad_down, int pad_right, int H, int
 // its sample points only (the x8 PAF maps are never written: PafScales::low)
 static size_t body_mid_heat(int N, const ScaleGeom& g) { return (size_t)N * 18 * g.Hs * g.Ws; }
 
+// The heat average of a pyramid (src/body.py:57-67, src/hand.py:53-56) into avg [N * C][H][W]:
+// scale s's x8 maps are frames [frame0, frame0 + N) of mid set s ([.][C][Hs][Ws]).  Every scale in
+// one launch with the average written once (heat_full_scales) where the handle allows it and the
+// scales fit, else a launch per scale; f32: one scale, whose average is exactly its float32
+// resize -> avg holds a float map.  mid_per_scale: the per-scale profile entries also book the
+// mid bytes they read (the body path's do, the hand path's do not).
+static void heat_average(opose_ctx* h, int N, int C, int frame0, int H, int W, const std::vector<ScaleGeom>& gs,
+                         bool f32, bool mid_per_scale, double* avg) {
+    const int ns = (int)gs.size();
+    auto mid = [&](int s) { return h->mid(s).ensure<float>(0, h->stream) + (size_t)frame0 * C * gs[s].Hs * gs[s].Ws; };
+    ProfEntry pe;
+    HeatScales hsc{};
+    hsc.n = ns;
+    hsc.ns = (float)ns;
+    double mid_bytes = 0;
+    for (int s = 0; s < ns && s < kHeatScales; ++s) {
+        hsc.s[s] = HeatScale{mid(s), C, 0, gs[s].Hs, gs[s].Ws, gs[s].up_sy, gs[s].up_sx};
+        mid_bytes += (double)N * C * 4.0 * gs[s].Hs * gs[s].Ws;
+    }
+    if (!f32 && h->heat_scales && heat_full_scales_fits(hsc, H, W)) {
+        h->prof_begin(pe, "heat_full", 0, (double)N * C * H * W * 8.0 + mid_bytes);
+        launch_heat_full_scales(hsc, N, C, H, W, avg, h->stream);
+        h->prof_end(pe);
+        return;
+    }
+    for (int s = 0; s < ns; ++s) {
+        h->prof_begin(pe, "heat_full", 0,
+                      (double)N * C * (H * W * (f32 ? 4.0 : 8.0) * (s ? 2 : 1) +
+                                       (mid_per_scale ? 4.0 * gs[s].Hs * gs[s].Ws : 0.0)));
+        if (f32)
+            launch_heat_full_f32(mid(s), C, 0, C, N, gs[s].Hs, gs[s].Ws, H, W, gs[s].up_sy, gs[s].up_sx,
+                                 reinterpret_cast<float*>(avg), h->stream);
+        else
+            launch_heat_full(mid(s), C, 0, C, N, gs[s].Hs, gs[s].Ws, H, W, gs[s].up_sy, gs[s].up_sx, ns, s > 0, avg,
+                             h->stream);
+        h->prof_end(pe);
+    }
+}
+
 // Second half of the body post path, shared by Body (body_post_common) and Batch_body
 // (batch_post_common): the peak-list and matching workspace, then find_peaks(cap, cnt, list, lscore)
 // (the caller's NMS over its part maps), then peaks_finalize .. assemble into the records.
@@ -119,32 +158,7 @@ void body_post_common(opose_ctx* h, int N, int H, int W, const std::vector<Scale
             return;
         }
         double* avg = h->avg.ensure<double>((size_t)N * 18 * H * W, h->stream);
-        HeatScales hsc{};
-        hsc.n = ns;
-        hsc.ns = (float)ns;
-        double mid_bytes = 0;
-        for (int s = 0; s < ns && s < kHeatScales; ++s) {
-            hsc.s[s] = HeatScale{S.mid[s], 18, 0, gs[s].Hs, gs[s].Ws, gs[s].up_sy, gs[s].up_sx};
-            mid_bytes += (double)N * 18 * 4.0 * gs[s].Hs * gs[s].Ws;
-        }
-        // several scales: one launch
-        const bool fused_avg = !f32 && h->heat_scales && heat_full_scales_fits(hsc, H, W);
-        if (fused_avg) {
-            h->prof_begin(pe, "heat_full", 0, (double)N * 18 * H * W * 8.0 + mid_bytes);
-            launch_heat_full_scales(hsc, N, 18, H, W, avg, h->stream);
-            h->prof_end(pe);
-        }
-        for (int s = 0; s < ns && !fused_avg; ++s) {
-            h->prof_begin(pe, "heat_full", 0,
-                          (double)N * 18 * (H * W * (f32 ? 4.0 : 8.0) * (s ? 2 : 1) + 4.0 * gs[s].Hs * gs[s].Ws));
-            if (f32)
-                launch_heat_full_f32(S.mid[s], 18, 0, 18, N, gs[s].Hs, gs[s].Ws, H, W, gs[s].up_sy, gs[s].up_sx,
-                                     reinterpret_cast<float*>(avg), h->stream);
-            else
-                launch_heat_full(S.mid[s], 18, 0, 18, N, gs[s].Hs, gs[s].Ws, H, W, gs[s].up_sy, gs[s].up_sx, ns,
-                                 s > 0, avg, h->stream);
-            h->prof_end(pe);
-        }
+        heat_average(h, N, 18, 0, H, W, gs, f32, true, avg);
         h->prof_begin(pe, "gauss_nms", 0, (double)N * 18 * H * W * (f32 ? 4 : 8));
         launch_gauss_nms(avg, f32, N * 18, H, W, p.thre1, cap, cnt, list, lscore, h->stream);
         h->prof_end(pe);
@@ -204,52 +218,39 @@ void batch_post_common(opose_ctx* h, int N, int H, int W, const float* maps, int
     });
 }
 
+// where a hand call writes its NP peaks and found flags on the device, from crop slot out_crop on:
+// the caller's buffers (OPOSE_OUT_DEVICE) or the handle's, which hand_finish copies to the host
+struct HandDest {
+    double* peaks;
+    int* found;
+};
+static HandDest hand_dest(opose_ctx* h, int NP, double* peaks_out, int32_t* found_out, int flags, int out_crop) {
+    const bool od = flags & OPOSE_OUT_DEVICE;
+    const size_t first = (size_t)out_crop * 21;
+    return {(od ? peaks_out : h->hpeaks.ensure<double>((first + NP) * 3, h->stream)) + first * 3,
+            (od ? found_out : h->hfound.ensure<int>(first + NP, h->stream)) + first};
+}
+
 // Hand post path from per-scale x8 maps (mids[s] = [N][21][Hs][Ws]) to peaks / found.
 // mid_crop: first crop of this call inside mids[s] (crop-batched hand path); out_crop: first
 // crop's slot in the peaks / found outputs
 void hand_post_common(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, const opose_params& p,
                       double* peaks_out, int32_t* found_out, int flags, int mid_crop, int out_crop) {
-    const int ns = (int)gs.size();
     const int NP = N * 21;
     double* avg = h->avg.ensure<double>((size_t)NP * H * W, h->stream);
     ProfEntry pe;
-    HeatScales hsc{};
-    hsc.n = ns;
-    hsc.ns = (float)ns;
-    double mid_bytes = 0;
-    for (int s = 0; s < ns && s < kHeatScales; ++s) {
-        hsc.s[s] = HeatScale{h->mid(s).ensure<float>(0, h->stream) + (size_t)mid_crop * 21 * gs[s].Hs * gs[s].Ws, 21, 0,
-                             gs[s].Hs, gs[s].Ws, gs[s].up_sy, gs[s].up_sx};
-        mid_bytes += (double)NP * 4.0 * gs[s].Hs * gs[s].Ws;
-    }
-    if (h->heat_scales && heat_full_scales_fits(hsc, H, W)) {  // every scale in one launch, the average written once
-        h->prof_begin(pe, "heat_full", 0, (double)NP * H * W * 8 + mid_bytes);
-        launch_heat_full_scales(hsc, N, 21, H, W, avg, h->stream);
-        h->prof_end(pe);
-    } else {
-        for (int s = 0; s < ns; ++s) {
-            h->prof_begin(pe, "heat_full", 0, (double)NP * H * W * 8 * (s ? 2 : 1));
-            const float* mid = h->mid(s).ensure<float>(0, h->stream) + (size_t)mid_crop * 21 * gs[s].Hs * gs[s].Ws;
-            launch_heat_full(mid, 21, 0, 21, N, gs[s].Hs, gs[s].Ws, H, W, gs[s].up_sy, gs[s].up_sx, ns, s > 0, avg,
-                             h->stream);
-            h->prof_end(pe);
-        }
-    }
+    heat_average(h, N, 21, mid_crop, H, W, gs, false, false, avg);
     int* lab = h->hlab.ensure<int>((size_t)NP * H * W, h->stream);
     double* sums = h->hsums.ensure<double>((size_t)NP * H * W, h->stream);
     int* cnt = h->cnt.ensure<int>((size_t)NP, h->stream);
-    double* pk = ((flags & OPOSE_OUT_DEVICE) ? peaks_out
-                                             : h->hpeaks.ensure<double>((size_t)(out_crop * 21 + NP) * 3, h->stream)) +
-                 (size_t)out_crop * 21 * 3;
-    int* fd = ((flags & OPOSE_OUT_DEVICE) ? found_out : h->hfound.ensure<int>((size_t)(out_crop * 21 + NP), h->stream)) +
-              (size_t)out_crop * 21;
+    const HandDest d = hand_dest(h, NP, peaks_out, found_out, flags, out_crop);
     OPOSE_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * NP, h->stream));
     h->prof_begin(pe, "gauss_threshold", 0, (double)NP * H * W * 12);
     launch_gauss_threshold(avg, NP, H, W, p.thre_hand, lab, cnt, sums, h->stream);
     h->prof_end(pe);
     h->prof_begin(pe, "hand_cc", 0, 0);
     void* ws = h->hsel.ensure<uint8_t>(hand_cc_workspace_bytes(NP), h->stream);
-    launch_hand_cc(avg, NP, H, W, lab, sums, cnt, pk, fd, ws, true, h->stream);
+    launch_hand_cc(avg, NP, H, W, lab, sums, cnt, d.peaks, d.found, ws, true, h->stream);
     h->prof_end(pe);
 }
 
@@ -284,16 +285,14 @@ void batch_hand_post_common(opose_ctx* h, int N, int H, int W, const float* maps
     int* lab = h->hlab.ensure<int>((size_t)NP * H * W, h->stream);
     double* sums = h->hsums.ensure<double>((size_t)NP * H * W, h->stream);
     int* cnt = h->cnt.ensure<int>((size_t)NP, h->stream);
-    const bool od = flags & OPOSE_OUT_DEVICE;
-    double* pk = od ? peaks : h->hpeaks.ensure<double>((size_t)NP * 3, h->stream);
-    int* fo = od ? found : h->hfound.ensure<int>((size_t)NP, h->stream);
+    const HandDest d = hand_dest(h, NP, peaks, found, flags, 0);
     OPOSE_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * NP, h->stream));
     h->prof_begin(pe, "gauss_threshold", 0, (double)NP * H * W * 16);
     launch_blur5_seed(mid, NP, H, W, p.thre_hand, avg, lab, cnt, h->stream);
     h->prof_end(pe);
     h->prof_begin(pe, "hand_cc", 0, 0);
     void* ws = h->hsel.ensure<uint8_t>(hand_cc_workspace_bytes(NP), h->stream);
-    launch_hand_cc(avg, NP, H, W, lab, sums, cnt, pk, fo, ws, false, h->stream);
+    launch_hand_cc(avg, NP, H, W, lab, sums, cnt, d.peaks, d.found, ws, false, h->stream);
     h->prof_end(pe);
     hand_finish(h, N, peaks, found, flags & OPOSE_OUT_DEVICE);
 }

@@ -16,34 +16,9 @@
 // resolve differently).
 #include "common.h"
 #include "kernels.h"
+#include "unionfind.h"
 
 namespace opose {
-
-__device__ __forceinline__ int uf_find(const int* L, int x) {
-    int p = L[x];
-    while (p != x) {
-        x = p;
-        p = L[x];
-    }
-    return x;
-}
-
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-    for (;;) {
-        a = uf_find(L, a);
-        b = uf_find(L, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        // link root a (larger) under b; succeeds iff a was still a root
-        const int old = atomicMin(L + a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
 
 // lab: [NP][H*W] seeds (-1, or the start of the pixel's run within its 64-pixel row segment,
 // see gauss_threshold).  8-connectivity with one union per run contact instead of four per
@@ -76,14 +51,12 @@ __global__ __launch_bounds__(256) void cc_union(int* __restrict__ lab, int H, in
 // tile-local root): join components across tile edges.  One thread per pixel of a tile's top row
 // (links to the three pixels above it) and of its left column (links to the three pixels left of
 // it) -- every 8-adjacent pair of set pixels in different tiles is one of these.
-constexpr int kSeedTW = 64, kSeedTH = 32;
-
 __global__ __launch_bounds__(128) void cc_border(int* __restrict__ lab, int H, int W, int ntx) {
     const int tx = blockIdx.x % ntx, ty = blockIdx.x / ntx, np = blockIdx.y;
-    const int x0 = tx * kSeedTW, y0 = ty * kSeedTH;
+    const int x0 = tx * TW, y0 = ty * TH;
     int* L = lab + (size_t)np * H * W;
     const int t = threadIdx.x;
-    if (t < kSeedTW) {  // top row: (y0 - 1, x - 1 .. x + 1)
+    if (t < TW) {  // top row: (y0 - 1, x - 1 .. x + 1)
         const int x = x0 + t, y = y0;
         if (y0 == 0 || x >= W || y >= H) return;
         const int i = y * W + x;
@@ -92,8 +65,8 @@ __global__ __launch_bounds__(128) void cc_border(int* __restrict__ lab, int H, i
             const int xx = x + dx;
             if (xx >= 0 && xx < W && L[i - W + dx] >= 0) uf_union(L, i, i - W + dx);
         }
-    } else if (t < kSeedTW + kSeedTH) {  // left column: (y - 1 .. y + 1, x0 - 1)
-        const int x = x0, y = y0 + t - kSeedTW;
+    } else if (t < TW + TH) {  // left column: (y - 1 .. y + 1, x0 - 1)
+        const int x = x0, y = y0 + t - TW;
         if (x0 == 0 || y >= H) return;
         const int i = y * W + x;
         if (L[i] < 0) return;
@@ -228,8 +201,7 @@ void launch_hand_cc(double* avg, int NP, int H, int W, int* lab, double* sums, c
                     int* found, void* ws, bool tile_seeds, hipStream_t st) {
     dim3 grid((W + 255) / 256, H, NP);
     if (tile_seeds) {
-        int ntx, nty;
-        gauss_threshold_tiles(H, W, &ntx, &nty);
+        const int ntx = (W + TW - 1) / TW, nty = (H + TH - 1) / TH;
         hipLaunchKernelGGL(cc_border, dim3(ntx * nty, NP), dim3(128), 0, st, lab, H, W, ntx);
     } else {
         hipLaunchKernelGGL(cc_union, grid, dim3(256), 0, st, lab, H, W);

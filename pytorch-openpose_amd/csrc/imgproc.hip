@@ -102,6 +102,36 @@ constexpr int RS_RT = 16;      // output rows per workgroup
 constexpr int RS_MAXR = 44;    // staged source rows (RT * scale + 5 <= 44  <=>  scale <= 2.4)
 constexpr int RS_CHUNK = 8;    // staged rows loaded per round
 
+// The horizontal pass of source rows r_lo .. r_hi of `plane` (ws floats per row) at this thread's
+// output column (taps tx) into its column of hs.  RS_CHUNK rows per round with every load issued
+// before the first use (rows past r_hi re-read r_hi and are not stored): a row-at-a-time loop
+// waited out one memory round trip per staged row
+template <int MAXR>
+__device__ __forceinline__ void stage_rows(const float* __restrict__ plane, int ws, int r_lo, int r_hi,
+                                           const CubicTap& tx, float (*hs)[256]) {
+    for (int k0 = 0; k0 < MAXR && r_lo + k0 <= r_hi; k0 += RS_CHUNK) {
+        float p[RS_CHUNK][4];
+#pragma unroll
+        for (int k = 0; k < RS_CHUNK; ++k) {
+            const float* row = plane + (size_t)min(r_lo + k0 + k, r_hi) * ws;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p[k][j] = row[tx.i[j]];
+        }
+#pragma unroll
+        for (int k = 0; k < RS_CHUNK; ++k) {
+            const float v = cubic_dot4(p[k][0], p[k][1], p[k][2], p[k][3], tx.c);
+            if (k0 + k < MAXR && r_lo + k0 + k <= r_hi) hs[k0 + k][threadIdx.x] = v;
+        }
+    }
+}
+
+// the vertical pass of one output row (taps ty) over this thread's column of the staged rows
+__device__ __forceinline__ float combine_rows(const float (*hs)[256], int r_lo, const CubicTap& ty) {
+    const int tid = threadIdx.x;
+    return cubic_dot4(hs[ty.i[0] - r_lo][tid], hs[ty.i[1] - r_lo][tid], hs[ty.i[2] - r_lo][tid],
+                      hs[ty.i[3] - r_lo][tid], ty.c);
+}
+
 // MAXR: LDS rows actually staged (8 for x8, 16 for x2): small tiles keep many workgroups
 // resident, which this HBM-bound kernel needs
 template <int MODE, int MAXR>
@@ -123,38 +153,12 @@ __global__ __launch_bounds__(256) void cubic_resize_rows(const float* __restrict
     const int r_hi = cubic_tap_any(y1 - 1, sy, hi, torch).i[3];
     const bool live = x < wo;
     if (tid < y1 - y0) s_ty[tid] = cubic_tap_any(y0 + tid, sy, hi, torch);
-    if (live) {
-        const CubicTap tx = cubic_tap_any(x, sx, wi, torch);
-        // RS_CHUNK rows per round with every load issued before the first use (rows past r_hi
-        // re-read r_hi and are not stored): a row-at-a-time loop waited out one memory round
-        // trip per staged row
-        for (int k0 = 0; k0 < MAXR && r_lo + k0 <= r_hi; k0 += RS_CHUNK) {
-            float p[RS_CHUNK][4];
-#pragma unroll
-            for (int k = 0; k < RS_CHUNK; ++k) {
-                const float* row = plane + (size_t)min(r_lo + k0 + k, r_hi) * wi;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) p[k][j] = row[tx.i[j]];
-            }
-#pragma unroll
-            for (int k = 0; k < RS_CHUNK; ++k) {
-                float v = p[k][0] * tx.c[0];
-                v = v + p[k][1] * tx.c[1];
-                v = v + p[k][2] * tx.c[2];
-                v = v + p[k][3] * tx.c[3];
-                if (k0 + k < MAXR && r_lo + k0 + k <= r_hi) hs[k0 + k][tid] = v;
-            }
-        }
-    }
+    if (live) stage_rows<MAXR>(plane, wi, r_lo, r_hi, cubic_tap_any(x, sx, wi, torch), hs);
     __syncthreads();
     if (!live) return;
     const bool div = nscales != 1.f;  // x / 1.0f == x exactly: skip the IEEE division sequence
     for (int y = y0; y < y1; ++y) {
-        const CubicTap ty = s_ty[y - y0];
-        float o = hs[ty.i[0] - r_lo][tid] * ty.c[0];
-        o = o + hs[ty.i[1] - r_lo][tid] * ty.c[1];
-        o = o + hs[ty.i[2] - r_lo][tid] * ty.c[2];
-        o = o + hs[ty.i[3] - r_lo][tid] * ty.c[3];
+        const float o = combine_rows(hs, r_lo, s_ty[y - y0]);
         const size_t e = ((size_t)nc * ho + y) * wo + x;
         if constexpr (MODE == 0) {
             reinterpret_cast<float*>(out)[e] = o;
@@ -208,36 +212,13 @@ __global__ __launch_bounds__(256) void heat_full_scales(HeatScales S, int P, int
         const int r_hi = cubic_tap(y1 - 1, g.sy, g.Hs).i[3];
         __syncthreads();  // the previous scale's staged rows are consumed
         if (tid < y1 - y0) s_ty[tid] = cubic_tap(y0 + tid, g.sy, g.Hs);
-        if (live) {
-            const CubicTap tx = cubic_tap(x, g.sx, g.Ws);
-            for (int k0 = 0; k0 < MAXR && r_lo + k0 <= r_hi; k0 += RS_CHUNK) {
-                float q[RS_CHUNK][4];
-#pragma unroll
-                for (int k = 0; k < RS_CHUNK; ++k) {
-                    const float* row = plane + (size_t)min(r_lo + k0 + k, r_hi) * g.Ws;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) q[k][j] = row[tx.i[j]];
-                }
-#pragma unroll
-                for (int k = 0; k < RS_CHUNK; ++k) {
-                    float v = q[k][0] * tx.c[0];
-                    v = v + q[k][1] * tx.c[1];
-                    v = v + q[k][2] * tx.c[2];
-                    v = v + q[k][3] * tx.c[3];
-                    if (k0 + k < MAXR && r_lo + k0 + k <= r_hi) hs[k0 + k][tid] = v;
-                }
-            }
-        }
+        if (live) stage_rows<MAXR>(plane, g.Ws, r_lo, r_hi, cubic_tap(x, g.sx, g.Ws), hs);
         __syncthreads();
         if (live) {
 #pragma unroll
             for (int r = 0; r < RS_RT; ++r)
                 if (y0 + r < y1) {
-                    const CubicTap ty = s_ty[r];
-                    float o = hs[ty.i[0] - r_lo][tid] * ty.c[0];
-                    o = o + hs[ty.i[1] - r_lo][tid] * ty.c[1];
-                    o = o + hs[ty.i[2] - r_lo][tid] * ty.c[2];
-                    o = o + hs[ty.i[3] - r_lo][tid] * ty.c[3];
+                    const float o = combine_rows(hs, r_lo, s_ty[r]);
                     const float v = div ? o / S.ns : o;
                     acc[r] = acc[r] + (double)v;
                 }
@@ -252,10 +233,13 @@ __global__ __launch_bounds__(256) void heat_full_scales(HeatScales S, int P, int
 // staged rows needed by one workgroup for a source step `scale` (destination -> source)
 static bool rows_fit(double scale) { return RS_RT * scale + 5.0 <= (double)RS_MAXR; }
 
+// grid of the row-staged kernels: RS_RT rows x 256 columns of one of NC planes per workgroup
+static dim3 rows_grid(int W, int H, int NC) { return dim3((W + 255) / 256, (H + RS_RT - 1) / RS_RT, NC); }
+
 template <int MODE>
-static void launch_resize_rows(dim3 grid, hipStream_t st, const float* in, int cstride, int coff, int C, int hi,
-                               int wi, int ho, int wo, double sy, double sx, float ns, int acc, void* out,
-                               int torch = 0) {
+static void launch_resize_rows(hipStream_t st, const float* in, int cstride, int coff, int C, int N, int hi, int wi,
+                               int ho, int wo, double sy, double sx, float ns, int acc, void* out, int torch = 0) {
+    const dim3 grid = rows_grid(wo, ho, N * C);
     const double need = RS_RT * sy + 5.0;
     if (need <= 8.0)
         hipLaunchKernelGGL((cubic_resize_rows<MODE, 8>), grid, dim3(256), 0, st, in, cstride, coff, C, hi, wi, ho, wo,
@@ -277,20 +261,32 @@ void launch_preprocess(const uint8_t* src, int64_t frame_stride, int64_t row_str
 
 void launch_upsample8(const float* in, int in_cstride, int in_coff, int C, int N, int hl, int wl, int Hs, int Ws,
                       float* out, hipStream_t st) {
-    dim3 grid((Ws + 255) / 256, (Hs + RS_RT - 1) / RS_RT, N * C);
-    launch_resize_rows<0>(grid, st, in, in_cstride, in_coff, C, hl, wl, Hs, Ws, 0.125, 0.125, 1.f, 0, (void*)out);
+    launch_resize_rows<0>(st, in, in_cstride, in_coff, C, N, hl, wl, Hs, Ws, 0.125, 0.125, 1.f, 0, (void*)out);
+}
+
+// heat_full of one scale (T = double: the float64 average, (+)=; float: the single-scale map):
+// the row-staged resize where its rows fit, else (and for an identity scale) a thread per pixel
+template <typename T>
+static void heat_full(const float* mid, int Cm, int coff, int P, int N, int Hs, int Ws, int H, int W, double sy,
+                      double sx, float ns, int accumulate, T* avg, hipStream_t st) {
+    if (!(Hs == H && Ws == W) && rows_fit(sy)) {
+        launch_resize_rows<sizeof(T) == 4 ? 1 : 2>(st, mid, Cm, coff, P, N, Hs, Ws, H, W, sy, sx, ns, accumulate,
+                                                   (void*)avg);
+        return;
+    }
+    dim3 grid((W + 255) / 256, H, N * P);
+    hipLaunchKernelGGL(heat_full_accum<T>, grid, dim3(256), 0, st, mid, Cm, coff, P, Hs, Ws, H, W, sy, sx, ns,
+                       accumulate, avg);
 }
 
 void launch_heat_full(const float* mid, int Cm, int coff, int P, int N, int Hs, int Ws, int H, int W, double sy,
                       double sx, int nscales, int accumulate, double* avg, hipStream_t st) {
-    if (!(Hs == H && Ws == W) && rows_fit(sy)) {
-        dim3 grid((W + 255) / 256, (H + RS_RT - 1) / RS_RT, N * P);
-        launch_resize_rows<2>(grid, st, mid, Cm, coff, P, Hs, Ws, H, W, sy, sx, (float)nscales, accumulate, (void*)avg);
-        return;
-    }
-    dim3 grid((W + 255) / 256, H, N * P);
-    hipLaunchKernelGGL(heat_full_accum<double>, grid, dim3(256), 0, st, mid, Cm, coff, P, Hs, Ws, H, W, sy, sx,
-                       (float)nscales, accumulate, avg);
+    heat_full(mid, Cm, coff, P, N, Hs, Ws, H, W, sy, sx, (float)nscales, accumulate, avg, st);
+}
+
+void launch_heat_full_f32(const float* mid, int Cm, int coff, int P, int N, int Hs, int Ws, int H, int W, double sy,
+                          double sx, float* avg, hipStream_t st) {
+    heat_full(mid, Cm, coff, P, N, Hs, Ws, H, W, sy, sx, 1.f, 0, avg, st);
 }
 
 bool heat_full_scales_fits(const HeatScales& S, int H, int W) {
@@ -301,20 +297,7 @@ bool heat_full_scales_fits(const HeatScales& S, int H, int W) {
 
 void launch_heat_full_scales(const HeatScales& S, int N, int P, int H, int W, double* avg, hipStream_t st) {
     if (!heat_full_scales_fits(S, H, W)) throw std::invalid_argument("heat_full_scales: scale out of range");
-    dim3 grid((W + 255) / 256, (H + RS_RT - 1) / RS_RT, N * P);
-    hipLaunchKernelGGL(heat_full_scales<RS_MAXR>, grid, dim3(256), 0, st, S, P, H, W, avg);
-}
-
-void launch_heat_full_f32(const float* mid, int Cm, int coff, int P, int N, int Hs, int Ws, int H, int W, double sy,
-                          double sx, float* avg, hipStream_t st) {
-    if (!(Hs == H && Ws == W) && rows_fit(sy)) {
-        dim3 grid((W + 255) / 256, (H + RS_RT - 1) / RS_RT, N * P);
-        launch_resize_rows<1>(grid, st, mid, Cm, coff, P, Hs, Ws, H, W, sy, sx, 1.f, 0, (void*)avg);
-        return;
-    }
-    dim3 grid((W + 255) / 256, H, N * P);
-    hipLaunchKernelGGL(heat_full_accum<float>, grid, dim3(256), 0, st, mid, Cm, coff, P, Hs, Ws, H, W, sy, sx, 1.f, 0,
-                       avg);
+    hipLaunchKernelGGL(heat_full_scales<RS_MAXR>, rows_grid(W, H, N * P), dim3(256), 0, st, S, P, H, W, avg);
 }
 
 // ---------------------------------------------------------------- Batch_body fast mode
@@ -346,17 +329,15 @@ __global__ __launch_bounds__(256) void preprocess_torch_u8(const uint8_t* __rest
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const uint8_t* row = f + (size_t)ty.i[r] * row_stride;
+            // cubic_dot4 over the four x / 255.f, spelled out: as its arguments the divisions are
+            // all scheduled before the first product (3 more VGPRs, 4 more waits)
             float v = (float)row[3 * tx.i[0] + c] / 255.f * tx.c[0];
             v = v + (float)row[3 * tx.i[1] + c] / 255.f * tx.c[1];
             v = v + (float)row[3 * tx.i[2] + c] / 255.f * tx.c[2];
             v = v + (float)row[3 * tx.i[3] + c] / 255.f * tx.c[3];
             h[r] = v;
         }
-        float v = h[0] * ty.c[0];
-        v = v + h[1] * ty.c[1];
-        v = v + h[2] * ty.c[2];
-        v = v + h[3] * ty.c[3];
-        o[(size_t)c * plane] = v - 0.5f;
+        o[(size_t)c * plane] = cubic_dot4(h[0], h[1], h[2], h[3], ty.c) - 0.5f;
     }
 }
 
@@ -370,8 +351,7 @@ void launch_preprocess_torch(const uint8_t* src, int64_t frame_stride, int64_t r
 // torch bicubic x8 of channels [in_coff, in_coff + C) cropped to nh x nw (scale 1/8 exactly)
 void launch_upsample8_torch(const float* in, int in_cstride, int in_coff, int C, int N, int hl, int wl, int nh, int nw,
                             float* out, hipStream_t st) {
-    dim3 grid((nw + 255) / 256, (nh + RS_RT - 1) / RS_RT, N * C);
-    launch_resize_rows<0>(grid, st, in, in_cstride, in_coff, C, hl, wl, nh, nw, 0.125, 0.125, 1.f, 0, (void*)out, 1);
+    launch_resize_rows<0>(st, in, in_cstride, in_coff, C, N, hl, wl, nh, nw, 0.125, 0.125, 1.f, 0, (void*)out, 1);
 }
 
 // torch bicubic to H x W (size given: scale = float(nh) / float(H)); float map out
@@ -379,8 +359,7 @@ void launch_resize_torch_f32(const float* mid, int Cm, int coff, int P, int N, i
                              float* out, hipStream_t st) {
     const float sy = (float)nh / (float)H, sx = (float)nw / (float)W;
     if (!rows_fit(sy)) throw std::invalid_argument("fast mode: downscale too strong for the staged resize");
-    dim3 grid((W + 255) / 256, (H + RS_RT - 1) / RS_RT, N * P);
-    launch_resize_rows<1>(grid, st, mid, Cm, coff, P, nh, nw, H, W, (double)sy, (double)sx, 1.f, 0, (void*)out, 1);
+    launch_resize_rows<1>(st, mid, Cm, coff, P, N, nh, nw, H, W, (double)sy, (double)sx, 1.f, 0, (void*)out, 1);
 }
 
 }  // namespace opose

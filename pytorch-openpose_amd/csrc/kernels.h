@@ -142,7 +142,6 @@ void launch_blur5_seed(const float* heat, int NP, int H, int W, double thre, dou
 // sums: zeroed at every tile-local root (the component sums' only addresses; launch_hand_cc)
 void launch_gauss_threshold(const double* avg, int NP, int H, int W, double thre, int* lab, int* cnt, double* sums,
                             hipStream_t st);
-void gauss_threshold_tiles(int H, int W, int* ntx, int* nty);
 void launch_peaks_finalize(const int* cnt, const int* list, const double* list_score, int N, int H, int W,
                            const RecordLayout& L, uint8_t* records, int* peak_pos, int* part_cnt, hipStream_t st);
 void launch_paf_score(const PafScales& S, const int* peak_pos, const int* part_cnt, int N, int cap, double thre2,

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "cubic.h"
 #include "kernels.h"
+#include "unionfind.h"
 
 namespace opose {
 
@@ -38,9 +39,67 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
     return i < n ? i : p - 1 - i;
 }
 
+// output i of the 25-tap filter over a window whose entry i + 12 is the centre: scipy's order,
+// the centre tap, then the symmetric pairs |j| = 12 .. 1, float64, no FMA
+__device__ __forceinline__ double gauss25(const double* win, int i) {
+    double acc = win[i + 12] * kGauss[0];
+#pragma unroll
+    for (int j = 12; j >= 1; --j) acc = acc + (win[i + 12 - j] + win[i + 12 + j]) * kGauss[j];
+    return acc;
+}
+
+// 1-D grid of TILE_W x TILE_H tiles over NP maps, and a workgroup's tile in it: (x0, y0) of map
+// np, in an XCD-contiguous order (guide T1) -- horizontally and vertically adjacent tiles, which
+// re-read each other's halos, share an L2
+template <int TILE_W, int TILE_H>
+static int tile_count(int H, int W, int NP) {
+    return ((W + TILE_W - 1) / TILE_W) * ((H + TILE_H - 1) / TILE_H) * NP;
+}
+template <int TILE_W, int TILE_H>
+__device__ __forceinline__ void tile_coords(int H, int W, int& x0, int& y0, int& np) {
+    const int ntx = (W + TILE_W - 1) / TILE_W, nty = (H + TILE_H - 1) / TILE_H;
+    const int id = xcd_contiguous_id(gridDim.x, blockIdx.x);
+    const int tx = id % ntx, rest = id / ntx;
+    x0 = tx * TILE_W;
+    y0 = (rest % nty) * TILE_H;
+    np = rest / nty;
+}
+
+// a peak of map np (pixel index idx) into the part's list; cnt counts every peak, the list
+// keeps the first cap (peaks_finalize flags the overflow).  score() is evaluated for a kept peak
+// only: gauss_nms_resize's is a cubic resample
+template <typename Score>
+__device__ __forceinline__ void push_peak(int* __restrict__ cnt, int* __restrict__ list,
+                                          double* __restrict__ list_score, int np, int cap, int idx, Score score) {
+    const int slot = atomicAdd(cnt + np, 1);
+    if (slot < cap) {
+        list[(size_t)np * cap + slot] = idx;
+        list_score[(size_t)np * cap + slot] = score();
+    }
+}
+
+// 4-neighbour '>=' maximum test of tile pixel (r, c) = map pixel (y, x), value v = s[r + 1][c + 1]
+// of a smoothed tile with its 1-pixel ring; neighbours outside the map count as zero
+// (src/body.py:79-87 and findpeaks_torch pad with zeros)
+template <typename T, int LD>
+__device__ __forceinline__ bool nms4(const T (*s)[LD], int r, int c, int y, int x, int H, int W, T v) {
+    const T up = y > 0 ? s[r][c + 1] : T(0);
+    const T dn = y < H - 1 ? s[r + 2][c + 1] : T(0);
+    const T lf = x > 0 ? s[r + 1][c] : T(0);
+    const T rt = x < W - 1 ? s[r + 1][c + 2] : T(0);
+    return v >= up && v >= dn && v >= lf && v >= rt;
+}
+
+// first lane of the run of set lanes that holds `lane`; set = __ballot of the wave's pixels (a
+// wave = one 64-pixel row segment)
+__device__ __forceinline__ int run_start(unsigned long long set, int lane) {
+    const unsigned long long unset = ~set & ((1ull << lane) - 1);  // unset lanes below
+    return unset ? 64 - __clzll((long long)unset) : 0;
+}
+
 // Gaussian tile (the hand threshold, gauss_threshold; the body NMS uses the wide tile below):
-// TW x TH outputs of one map (+ the 1-pixel NMS ring).  scipy order: axis 0
-// (vertical) then axis 1, symmetric taps summed centre-first then |j| = 12 .. 1, float64, no FMA.
+// TW x TH (unionfind.h) outputs of one map (+ the 1-pixel NMS ring).  scipy order: axis 0
+// (vertical) then axis 1, gauss25 each.
 //  * vertical pass straight from global memory: a thread owns one column of the tile's
 //    13-pixel-haloed footprint and half its rows, sliding a 41-entry register window down the
 //    column (one load per input, coalesced across threads), result -> LDS v[VR][VW];
@@ -48,7 +107,6 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
 //  * NMS on the smoothed tile.
 // 64 x 32 outputs per tile: 2.6 filter evaluations per output pixel (halo included) instead
 // of 3.1 for 32 x 32 tiles, and no staged input tile (42 KB of LDS, 3 workgroups per CU).
-constexpr int TW = 64, TH = 32;
 constexpr int VW = TW + 26;   // vertical-pass columns: 13-pixel halo (12 filter + 1 ring) each side
 constexpr int VR = TH + 2;    // smoothed rows incl. the NMS ring
 constexpr int GW = TW + 2;    // smoothed cols incl. the NMS ring
@@ -88,12 +146,7 @@ __device__ __forceinline__ bool gauss_tile(const T* __restrict__ m, int H, int W
     if (!__syncthreads_or(hot)) return false;
     if (vt) {
 #pragma unroll
-        for (int i = 0; i < VH; ++i) {
-            double acc = win[i + 12] * kGauss[0];
-#pragma unroll
-            for (int j = 12; j >= 1; --j) acc = acc + (win[i + 12 - j] + win[i + 12 + j]) * kGauss[j];
-            t.v[h * VH + i][c] = acc;
-        }
+        for (int i = 0; i < VH; ++i) t.v[h * VH + i][c] = gauss25(win, i);
     }
     __syncthreads();
     if (tid < VR * 7) {  // axis 1: thread -> (row r, 10-column run)
@@ -102,33 +155,11 @@ __device__ __forceinline__ bool gauss_tile(const T* __restrict__ m, int H, int W
 #pragma unroll
         for (int i = 0; i < HC + 24; ++i) win[i] = (c0 + i < VW) ? t.v[r][c0 + i] : 0.0;
 #pragma unroll
-        for (int i = 0; i < HC; ++i) {
-            if (c0 + i < GW) {
-                double acc = win[i + 12] * kGauss[0];
-#pragma unroll
-                for (int j = 12; j >= 1; --j) acc = acc + (win[i + 12 - j] + win[i + 12 + j]) * kGauss[j];
-                t.g[r][c0 + i] = acc;
-            }
-        }
+        for (int i = 0; i < HC; ++i)
+            if (c0 + i < GW) t.g[r][c0 + i] = gauss25(win, i);
     }
     __syncthreads();
     return true;
-}
-
-// tile id -> (x tile, y tile, map) with an XCD-contiguous order (guide T1): horizontally and
-// vertically adjacent tiles, which re-read each other's 13-pixel halos, share an L2.
-__device__ __forceinline__ void gauss_tile_coords_of(int H, int W, int total, int b, int& x0, int& y0, int& np) {
-    const int ntx = (W + TW - 1) / TW, nty = (H + TH - 1) / TH;
-    const int q = total >> 3, rr = total & 7, xcd = b & 7;
-    const int id = xcd * q + min(xcd, rr) + (b >> 3);
-    const int tx = id % ntx, rest = id / ntx;
-    const int ty = rest % nty;
-    np = rest / nty;
-    x0 = tx * TW;
-    y0 = ty * TH;
-}
-__device__ __forceinline__ void gauss_tile_coords(int H, int W, int& x0, int& y0, int& np) {
-    gauss_tile_coords_of(H, W, gridDim.x, blockIdx.x, x0, y0, np);
 }
 
 // ---------------------------------------------------------------- Gaussian NMS (body peaks)
@@ -194,12 +225,7 @@ __device__ __forceinline__ void gauss_wide_tail(double (&win)[WVH + 24], double 
     for (int i = 0; i < WVH + 24; ++i) hot |= win[i] >= skip_below;
     if (!__syncthreads_or(hot)) return;  // no smoothed value can pass `> thre` (see gauss_tile)
 #pragma unroll
-    for (int i = 0; i < WVH; ++i) {
-        double acc = win[i + 12] * kGauss[0];
-#pragma unroll
-        for (int j = 12; j >= 1; --j) acc = acc + (win[i + 12 - j] + win[i + 12 + j]) * kGauss[j];
-        sv[h * WVH + i][c] = acc;
-    }
+    for (int i = 0; i < WVH; ++i) sv[h * WVH + i][c] = gauss25(win, i);
     __syncthreads();
     {
         const int r = tid & (WVR - 1), c0 = (tid >> 5) * WHC;
@@ -208,12 +234,7 @@ __device__ __forceinline__ void gauss_wide_tail(double (&win)[WVH + 24], double 
         for (int i = 0; i < WHC + 24; ++i) hw[i] = sv[r][c0 + i];
         __syncthreads();  // every thread holds its inputs: outputs go in place
 #pragma unroll
-        for (int i = 0; i < WHC; ++i) {
-            double acc = hw[i + 12] * kGauss[0];
-#pragma unroll
-            for (int j = 12; j >= 1; --j) acc = acc + (hw[i + 12 - j] + hw[i + 12 + j]) * kGauss[j];
-            sv[r][c0 + i] = acc;
-        }
+        for (int i = 0; i < WHC; ++i) sv[r][c0 + i] = gauss25(hw, i);
     }
     __syncthreads();
     for (int e = tid; e < WTW * WTH; e += 256) {
@@ -221,30 +242,9 @@ __device__ __forceinline__ void gauss_wide_tail(double (&win)[WVH + 24], double 
         const int y = y0 + r, x = x0 + cc;
         if (y >= H || x >= W) continue;
         const double v = sv[r + 1][cc + 1];
-        const double up = y > 0 ? sv[r][cc + 1] : 0.0;
-        const double dn = y < H - 1 ? sv[r + 2][cc + 1] : 0.0;
-        const double lf = x > 0 ? sv[r + 1][cc] : 0.0;
-        const double rt = x < W - 1 ? sv[r + 1][cc + 2] : 0.0;
-        if (v >= up && v >= dn && v >= lf && v >= rt && v > thre) {
-            const int slot = atomicAdd(cnt + np, 1);
-            if (slot < cap) {
-                list[(size_t)np * cap + slot] = y * W + x;
-                list_score[(size_t)np * cap + slot] = score_at(y, x);
-            }
-        }
+        if (nms4(sv, r, cc, y, x, H, W, v) && v > thre)
+            push_peak(cnt, list, list_score, np, cap, y * W + x, [&] { return score_at(y, x); });
     }
-}
-
-// wide tile id -> (x0, y0, map) in XCD-contiguous ranges (guide T1)
-__device__ __forceinline__ void gauss_wide_coords(int H, int W, int& x0, int& y0, int& np) {
-    const int ntx = (W + WTW - 1) / WTW, nty = (H + WTH - 1) / WTH;
-    const int total = gridDim.x, b = blockIdx.x;
-    const int q = total >> 3, rr = total & 7, xcd = b & 7;
-    const int id = xcd * q + min(xcd, rr) + (b >> 3);
-    const int tx = id % ntx, rest = id / ntx;
-    x0 = tx * WTW;
-    y0 = (rest % nty) * WTH;
-    np = rest / nty;
 }
 
 template <typename T>
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) void gauss_nms_wide(const T* __restrict__ avg,
                                                       double* __restrict__ list_score) {
     __shared__ double sv[WVR][WVW + 1];
     int x0, y0, np;
-    gauss_wide_coords(H, W, x0, y0, np);
+    tile_coords<WTW, WTH>(H, W, x0, y0, np);
     const T* m = avg + (size_t)np * H * W;
     const int tid = threadIdx.x;
     const int c = tid & (WVW - 1), h = tid >> 7;
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) void gauss_nms_resize(const float* __restrict_
     __shared__ int s_lo, s_hi;
     float (*hs)[WVW] = reinterpret_cast<float (*)[WVW]>(&sv[0][0]);
     int x0, y0, np;
-    gauss_wide_coords(H, W, x0, y0, np);
+    tile_coords<WTW, WTH>(H, W, x0, y0, np);
     const int n = np / P, p = np - n * P;
     const float* plane = mid + ((size_t)n * Cm + coff + p) * Hs * Ws;
     const int tid = threadIdx.x;
@@ -335,10 +335,7 @@ __global__ __launch_bounds__(256) void gauss_nms_resize(const float* __restrict_
             for (int k = 0; k < 8; ++k) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) mx = fmaxf(mx, fabsf(q[k][j]));
-                float v = q[k][0] * tx.c[0];
-                v = v + q[k][1] * tx.c[1];
-                v = v + q[k][2] * tx.c[2];
-                v = v + q[k][3] * tx.c[3];
+                const float v = cubic_dot4(q[k][0], q[k][1], q[k][2], q[k][3], tx.c);
                 if (r0 + 2 * k <= hi) hs[r0 + 2 * k - lo][c] = v;
             }
         }
@@ -349,10 +346,8 @@ __global__ __launch_bounds__(256) void gauss_nms_resize(const float* __restrict_
 #pragma unroll
     for (int i = 0; i < WVH + 24; ++i) {
         const CubicTap ty = s_ty[h * WVH + i];
-        float o = hs[ty.i[0] - lo][c] * ty.c[0];
-        o = o + hs[ty.i[1] - lo][c] * ty.c[1];
-        o = o + hs[ty.i[2] - lo][c] * ty.c[2];
-        o = o + hs[ty.i[3] - lo][c] * ty.c[3];
+        const float o =
+            cubic_dot4(hs[ty.i[0] - lo][c], hs[ty.i[1] - lo][c], hs[ty.i[2] - lo][c], hs[ty.i[3] - lo][c], ty.c);
         win[i] = (double)(0.f + o);
     }
     gauss_wide_tail(win, sv, H, W, x0, y0, np, thre, cap, cnt, list, list_score, [&](int y, int x) {
@@ -368,9 +363,8 @@ void launch_gauss_nms_resize(const float* mid, int Cm, int coff, int P, int N, i
                              double sx, double thre, int cap, int* cnt, int* list, double* list_score,
                              hipStream_t st) {
     if (!gauss_nms_resize_fits(Hs, Ws, H, W, sy)) throw std::invalid_argument("gauss_nms_resize: scale out of range");
-    const int tiles = ((W + WTW - 1) / WTW) * ((H + WTH - 1) / WTH) * N * P;
-    hipLaunchKernelGGL(gauss_nms_resize, dim3(tiles), dim3(256), 0, st, mid, Cm, coff, P, Hs, Ws, H, W, sy, sx, thre,
-                       cap, cnt, list, list_score);
+    hipLaunchKernelGGL(gauss_nms_resize, dim3(tile_count<WTW, WTH>(H, W, N * P)), dim3(256), 0, st, mid, Cm, coff, P,
+                       Hs, Ws, H, W, sy, sx, thre, cap, cnt, list, list_score);
 }
 
 // Hand: binary = gaussian_filter(map) > thre (src/hand.py:62-63) as union-find seeds, labelled
@@ -382,7 +376,7 @@ __global__ __launch_bounds__(256) void gauss_threshold(const double* __restrict_
     __shared__ GaussTile t;
     __shared__ int s_n;
     int x0, y0, np;
-    gauss_tile_coords(H, W, x0, y0, np);
+    tile_coords<TW, TH>(H, W, x0, y0, np);
     if (threadIdx.x == 0) s_n = 0;
     if (!gauss_tile(avg + (size_t)np * H * W, H, W, x0, y0, t, gauss_skip_below(thre))) {
         for (int e = threadIdx.x; e < TW * TH; e += 256) {  // nothing passes `> thre`
@@ -404,46 +398,22 @@ __global__ __launch_bounds__(256) void gauss_threshold(const double* __restrict_
     for (int e = threadIdx.x; e < TW * TH; e += 256) {
         const int r = e / TW, c = e - r * TW;
         const bool on = y0 + r < H && x0 + c < W && t.g[r + 1][c + 1] > thre;
-        const unsigned long long unset = ~__ballot(on) & ((1ull << lane) - 1);  // unset lanes below
-        const int start = unset ? 64 - __clzll((long long)unset) : 0;          // first lane of the run
+        const int start = run_start(__ballot(on), lane);
         sl[e] = on ? e - (lane - start) : -1;
         mine += on;
     }
     __syncthreads();
-    const volatile int* vsl = sl;  // re-read: other lanes relink roots concurrently
-    auto find = [&](int x) __attribute__((always_inline)) {
-        int p = vsl[x];
-        while (p != x) {
-            x = p;
-            p = vsl[x];
-        }
-        return x;
-    };
-    auto unite = [&](int a, int b) __attribute__((always_inline)) {
-        for (;;) {
-            a = find(a);
-            b = find(b);
-            if (a == b) return;
-            if (a < b) {
-                const int tmp = a;
-                a = b;
-                b = tmp;
-            }
-            const int old = atomicMin(sl + a, b);  // link root a (larger) under b
-            if (old == a) return;
-            a = old;
-        }
-    };
+    volatile int* vsl = sl;  // re-read: other lanes relink roots concurrently
     for (int e = threadIdx.x + TW; e < TW * TH; e += 256) {
         if (sl[e] < 0) continue;
         const int c = e & (TW - 1), u = e - TW;
         const bool left = c > 0 && sl[e - 1] >= 0;
         const bool ul = c > 0 && sl[u - 1] >= 0, up = sl[u] >= 0, ur = c + 1 < TW && sl[u + 1] >= 0;
         if (!left) {
-            if (ul) unite(e, u - 1);
-            if (up && !ul) unite(e, u);
+            if (ul) uf_union(vsl, e, u - 1);
+            if (up && !ul) uf_union(vsl, e, u);
         }
-        if (ur && !up) unite(e, u + 1);
+        if (ur && !up) uf_union(vsl, e, u + 1);
     }
     __syncthreads();
     for (int e = threadIdx.x; e < TW * TH; e += 256) {
@@ -452,7 +422,7 @@ __global__ __launch_bounds__(256) void gauss_threshold(const double* __restrict_
         if (y >= H || x >= W) continue;
         int g = -1;
         if (sl[e] >= 0) {
-            const int root = find(e);
+            const int root = uf_find(vsl, e);
             g = (y0 + root / TW) * W + x0 + (root & (TW - 1));
             // every component's root is one of its tiles' local roots: the sums cc_compress_sum
             // accumulates start from these zeros (no memset of the whole map)
@@ -463,12 +433,6 @@ __global__ __launch_bounds__(256) void gauss_threshold(const double* __restrict_
     if (mine) atomicAdd(&s_n, mine);
     __syncthreads();
     if (threadIdx.x == 0 && s_n) atomicAdd(cnt + np, s_n);
-}
-
-// tiles of gauss_threshold (per map); cc_border's grid
-void gauss_threshold_tiles(int H, int W, int* ntx, int* nty) {
-    *ntx = (W + TW - 1) / TW;
-    *nty = (H + TH - 1) / TH;
 }
 
 // ---------------------------------------------------------------- Batch_body fast mode
@@ -497,13 +461,8 @@ __global__ __launch_bounds__(256) void blur5_nms(const float* __restrict__ heat,
                                                  double* __restrict__ list_score) {
     __shared__ float s_in[BI][BI];
     __shared__ float s_b[BT + 2][BT + 2];
-    const int ntx = (W + BT - 1) / BT, nty = (H + BT - 1) / BT;
-    const int total = gridDim.x, b = blockIdx.x;
-    const int q = total >> 3, rr = total & 7, xcd = b & 7;
-    const int id = xcd * q + min(xcd, rr) + (b >> 3);
-    const int tx = id % ntx, rest = id / ntx;
-    const int ty = rest % nty, np = rest / nty;
-    const int x0 = tx * BT, y0 = ty * BT;
+    int x0, y0, np;
+    tile_coords<BT, BT>(H, W, x0, y0, np);
     const float* m = heat + (size_t)np * H * W;
     for (int e = threadIdx.x; e < BI * BI; e += 256) {
         const int r = e / BI, c = e - r * BI;
@@ -526,17 +485,9 @@ __global__ __launch_bounds__(256) void blur5_nms(const float* __restrict__ heat,
         const int y = y0 + r, x = x0 + c;
         if (y >= H || x >= W) continue;
         const float v = s_b[r + 1][c + 1];
-        const float up = y > 0 ? s_b[r][c + 1] : 0.f;     // findpeaks_torch pads with zeros
-        const float dn = y < H - 1 ? s_b[r + 2][c + 1] : 0.f;
-        const float lf = x > 0 ? s_b[r + 1][c] : 0.f;
-        const float rt = x < W - 1 ? s_b[r + 1][c + 2] : 0.f;
-        if (v > (float)thre && v >= up && v >= dn && v >= lf && v >= rt) {
-            const int slot = atomicAdd(cnt + np, 1);
-            if (slot < cap) {
-                list[(size_t)np * cap + slot] = y * W + x;
-                list_score[(size_t)np * cap + slot] = (double)v;  // the blurred value (Batch_model.py:191)
-            }
-        }
+        const bool top = nms4(s_b, r, c, y, x, H, W, v);  // before the branch: the neighbours load unconditionally
+        if (v > (float)thre && top)
+            push_peak(cnt, list, list_score, np, cap, y * W + x, [&] { return (double)v; });  // Batch_model.py:191
     }
 }
 
@@ -550,10 +501,10 @@ __global__ __launch_bounds__(256) void blur5_seed(const float* __restrict__ heat
                                                   int* __restrict__ cnt) {
     __shared__ float s_in[SH + 4][SW + 4];
     __shared__ int s_n;
+    // tile_coords<SW, SH>, spelled out: through the shared function this kernel's address
+    // arithmetic compiles differently (four more scalar instructions)
     const int ntx = (W + SW - 1) / SW, nty = (H + SH - 1) / SH;
-    const int total = gridDim.x, b = blockIdx.x;
-    const int q = total >> 3, rr = total & 7, xcd = b & 7;
-    const int id = xcd * q + min(xcd, rr) + (b >> 3);
+    const int id = xcd_contiguous_id(gridDim.x, blockIdx.x);
     const int tx = id % ntx, rest = id / ntx;
     const int ty = rest % nty, np = rest / nty;
     const int x0 = tx * SW, y0 = ty * SH;
@@ -576,8 +527,7 @@ __global__ __launch_bounds__(256) void blur5_seed(const float* __restrict__ heat
 #pragma unroll
             for (int dx = 0; dx < 5; ++dx) acc = acc + s_in[r + dy][c + dx] * kBlur5[dy][dx];
         const bool on = in && acc > (float)thre;
-        const unsigned long long unset = ~__ballot(on) & ((1ull << lane) - 1);
-        const int start = unset ? 64 - __clzll((long long)unset) : 0;
+        const int start = run_start(__ballot(on), lane);
         if (!in) continue;
         const size_t i = (size_t)y * W + x;
         blurred[(size_t)np * H * W + i] = (double)acc;
@@ -600,7 +550,7 @@ __global__ __launch_bounds__(128) void peaks_finalize(const int* __restrict__ cn
     const int n = blockIdx.x / 18, p = blockIdx.x - n * 18;
     const int cap = L.peaks_per_part;
     __shared__ int s_c, s_start;
-    __shared__ int s_v[1024];
+    __shared__ int s_v[kMaxPeaksPerPart];  // this part's peaks (c <= cap: launch_peaks_finalize checks cap)
     if (threadIdx.x < 64) {  // one wave: clamped counts, this part's start, the header (part 0)
         const int q = threadIdx.x;
         const int raw = q < 18 ? cnt[n * 18 + q] : 0;
@@ -629,15 +579,13 @@ __global__ __launch_bounds__(128) void peaks_finalize(const int* __restrict__ cn
     __syncthreads();
     const int c = s_c;
     const int* lp = list + ((size_t)n * 18 + p) * cap;
-    const bool staged = c <= 1024;
-    if (staged)
-        for (int i = threadIdx.x; i < c; i += blockDim.x) s_v[i] = lp[i];
+    for (int i = threadIdx.x; i < c; i += blockDim.x) s_v[i] = lp[i];
     __syncthreads();
     double* cand = reinterpret_cast<double*>(records + (size_t)n * L.bytes + L.cand_off);
     for (int i = threadIdx.x; i < c; i += blockDim.x) {
-        const int v = staged ? s_v[i] : lp[i];
+        const int v = s_v[i];
         int rank = 0;
-        for (int j = 0; j < c; ++j) rank += (staged ? s_v[j] : lp[j]) < v;
+        for (int j = 0; j < c; ++j) rank += s_v[j] < v;
         const int y = v / W, x = v - y * W;
         const int id = s_start + rank;
         double* row = cand + (size_t)id * 4;
@@ -697,11 +645,7 @@ __device__ __forceinline__ void resize_x8_pair(const float* __restrict__ lx, con
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const bool b = bx[j];
-                float v = (b ? p[1] : p[0]) * cxc[j][0];
-                v = v + (b ? p[2] : p[1]) * cxc[j][1];
-                v = v + (b ? p[3] : p[2]) * cxc[j][2];
-                v = v + (b ? p[4] : p[3]) * cxc[j][3];
-                hs[j][k] = v;
+                hs[j][k] = cubic_dot4(b ? p[1] : p[0], b ? p[2] : p[1], b ? p[3] : p[2], b ? p[4] : p[3], cxc[j]);
             }
         }
         float o = 0.f;
@@ -711,17 +655,10 @@ __device__ __forceinline__ void resize_x8_pair(const float* __restrict__ lx, con
             const bool b = by[r];
             float x8[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float u = (b ? hs[j][1] : hs[j][0]) * ry.c[0];
-                u = u + (b ? hs[j][2] : hs[j][1]) * ry.c[1];
-                u = u + (b ? hs[j][3] : hs[j][2]) * ry.c[2];
-                u = u + (b ? hs[j][4] : hs[j][3]) * ry.c[3];
-                x8[j] = u;
-            }
-            float v = x8[0] * tx.c[0];
-            v = v + x8[1] * tx.c[1];
-            v = v + x8[2] * tx.c[2];
-            v = v + x8[3] * tx.c[3];
+            for (int j = 0; j < 4; ++j)
+                x8[j] = cubic_dot4(b ? hs[j][1] : hs[j][0], b ? hs[j][2] : hs[j][1], b ? hs[j][3] : hs[j][2],
+                                   b ? hs[j][4] : hs[j][3], ry.c);
+            const float v = cubic_dot4(x8[0], x8[1], x8[2], x8[3], tx.c);
             o = r == 0 ? v * ty.c[0] : o + v * ty.c[r];
         }
         if (ch) oy = o;
@@ -1066,7 +1003,7 @@ __global__ __launch_bounds__(64) void assemble_people(const Conn* __restrict__ c
 // ------------------------------------------------------------------ launchers
 void launch_gauss_nms(const void* avg, bool f32, int NP, int H, int W, double thre, int cap, int* cnt, int* list,
                       double* list_score, hipStream_t st) {
-    const dim3 grid(((W + WTW - 1) / WTW) * ((H + WTH - 1) / WTH) * NP);
+    const dim3 grid(tile_count<WTW, WTH>(H, W, NP));
     if (f32)
         hipLaunchKernelGGL(gauss_nms_wide<float>, grid, dim3(256), 0, st, (const float*)avg, H, W, thre, cap, cnt,
                            list, list_score);
@@ -1077,24 +1014,25 @@ void launch_gauss_nms(const void* avg, bool f32, int NP, int H, int W, double th
 
 void launch_blur5_nms(const float* heat, int NP, int H, int W, double thre, int cap, int* cnt, int* list,
                       double* list_score, hipStream_t st) {
-    dim3 grid(((W + BT - 1) / BT) * ((H + BT - 1) / BT) * NP);
+    const dim3 grid(tile_count<BT, BT>(H, W, NP));
     hipLaunchKernelGGL(blur5_nms, grid, dim3(256), 0, st, heat, H, W, thre, cap, cnt, list, list_score);
 }
 
 void launch_blur5_seed(const float* heat, int NP, int H, int W, double thre, double* blurred, int* lab, int* cnt,
                        hipStream_t st) {
-    dim3 grid(((W + SW - 1) / SW) * ((H + SH - 1) / SH) * NP);
+    const dim3 grid(tile_count<SW, SH>(H, W, NP));
     hipLaunchKernelGGL(blur5_seed, grid, dim3(256), 0, st, heat, H, W, thre, blurred, lab, cnt);
 }
 
 void launch_gauss_threshold(const double* avg, int NP, int H, int W, double thre, int* lab, int* cnt, double* sums,
                             hipStream_t st) {
-    dim3 grid(((W + TW - 1) / TW) * ((H + TH - 1) / TH) * NP);
+    const dim3 grid(tile_count<TW, TH>(H, W, NP));
     hipLaunchKernelGGL(gauss_threshold, grid, dim3(256), 0, st, avg, H, W, thre, lab, cnt, sums);
 }
 
 void launch_peaks_finalize(const int* cnt, const int* list, const double* list_score, int N, int H, int W,
                            const RecordLayout& L, uint8_t* records, int* peak_pos, int* part_cnt, hipStream_t st) {
+    if (L.peaks_per_part > kMaxPeaksPerPart) throw std::invalid_argument("peaks_finalize: capacity out of range");
     hipLaunchKernelGGL(peaks_finalize, dim3(N * 18), dim3(128), 0, st, cnt, list, list_score, H, W, L, records,
                        peak_pos, part_cnt);
 }
@@ -1121,7 +1059,7 @@ void launch_assemble(const Conn* conn, const int* conn_cnt, const int* part_cnt,
     const size_t fit = sub < 64 * 1024 ? (64 * 1024 - sub) / kEntry : 0;
     const int stage = (int)std::max<size_t>((size_t)L.peaks_per_part, std::min<size_t>(19 * (size_t)L.peaks_per_part, fit));
     const size_t shm = sub + (size_t)stage * kEntry;
-    if (shm > 64 * 1024) {  // grown capacities (up to 256 people / 1024 peaks per part: 80 KB)
+    if (shm > 64 * 1024) {  // grown capacities (up to kMaxPeople / kMaxPeaksPerPart: 80 KB)
         static size_t granted = 0;
         if (shm > granted) {
             OPOSE_HIP_CHECK(hipFuncSetAttribute((const void*)assemble_people,

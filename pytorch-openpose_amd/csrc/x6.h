@@ -86,12 +86,8 @@ __device__ __forceinline__ f32x4 mfma_x6(const i32x4& a, const i32x4& b, f32x4 c
                                                    0, 0);
 }
 
-// XCD-contiguous workgroup id (guide T1): blocks b and b + 8 share an XCD, so XCD x takes the
-// ids [x G / 8, (x + 1) G / 8) and neighbouring tiles share its L2
-__device__ __forceinline__ int x6_xcd_id() {
-    const int G = gridDim.x, b = blockIdx.x, q = G >> 3, rr = G & 7, xcd = b & 7;
-    return xcd * q + min(xcd, rr) + (b >> 3);
-}
+// this workgroup's XCD-contiguous id (common.h)
+__device__ __forceinline__ int x6_xcd_id() { return xcd_contiguous_id(gridDim.x, blockIdx.x); }
 
 // bias of the tile's MT rows (first row m0) into LDS, 0 past cout
 __device__ __forceinline__ void x6_load_bias(float* s_bias, const X6Group& G, int m0, int MT) {

@@ -145,6 +145,15 @@ def test_rejection(native, case):
         assert native.lib.opose_last_error(handle.h)
 
 
+def test_set_capacity_limits(native):
+    """The largest capacities (1024 peaks per part, 256 people: csrc/common.h) are accepted, one
+    more of either is OPOSE_E_ARG."""
+    handle = native.Handle(0)
+    assert native.lib.opose_set_capacity(handle.h, 1024, 256) == native.OPOSE_OK
+    assert native.lib.opose_set_capacity(handle.h, 1025, 256) == native.OPOSE_E_ARG
+    assert native.lib.opose_set_capacity(handle.h, 1024, 257) == native.OPOSE_E_ARG
+
+
 def _same_people(got, exp):
     (c, s), (ec, es) = got, exp
     assert np.array_equal(c, ec) and np.array_equal(s, es)

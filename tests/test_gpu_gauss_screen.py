@@ -49,12 +49,19 @@ def test_screened_nms_single_scale(body, kind):
     assert np.array_equal(cand, ref_c) and np.array_equal(subset, ref_s)
 
 
-def test_screened_nms_two_scales_float64_average():
+@pytest.fixture(scope="module")
+def body2():
     from src.body import Body
     from src.weights import seeded_state_dict
+    return Body(seeded_state_dict("body", 0), scale_search=(0.5, 1.0))
+
+
+# 120 x 168: every tile of gauss_nms_wide<double> touches the map's border (reflected loads);
+# 120 x 240: the tile at (102, 30) is interior (W >= 217, H >= 73: the pointer-stepping loads)
+@pytest.mark.parametrize("hw", [(120, 168), (120, 240)], ids=lambda v: f"{v[0]}x{v[1]}")
+def test_screened_nms_two_scales_float64_average(body2, hw):
     rng = np.random.default_rng(7)
-    H, W = 120, 168
-    body2 = Body(seeded_state_dict("body", 0), scale_search=(0.5, 1.0))
+    H, W = hw
     geoms = body2.scale_geom(H, W)
     lowres, maps = [], []
     for (hl, wl, pd, pr) in geoms:

@@ -129,6 +129,43 @@ def test_heat_chain_bit_exact(native, handle):
         assert np.array_equal(paf_mid, np.transpose(mid, (2, 0, 1))), path
 
 
+# (hl, wl, pad_down, pad_right, H, W): one case per path of the heat resize (source step sy =
+# (8 hl - pad_down) / H); the golden frames above all land in one staged-rows bucket
+HEAT_BUCKETS = [
+    (6, 8, 0, 0, 260, 350),     # sy 0.185: cubic_resize_rows<2, 8>, two column blocks, the second partial
+    (12, 16, 3, 5, 160, 200),   # sy 0.581: <2, 16>, cropped source
+    (12, 16, 0, 0, 60, 80),     # sy 1.6: <2, 44>
+    (12, 16, 0, 0, 30, 40),     # sy 3.2: the staged rows do not fit, heat_full_accum<double> resizing
+    (12, 16, 0, 0, 96, 128),    # identity: heat_full_accum<double> copying
+]
+
+
+def heat_bucket_case(case):
+    """Random maps of a HEAT_BUCKETS case and the oracle's heat average / x8 PAF maps for them."""
+    from oracle.body_post import upsample_map
+    from oracle.cv_resize import resize_cubic
+    hl, wl, pad_down, pad_right, H, W = case
+    rng = np.random.default_rng(hl * 1000 + H)
+    maps = rng.standard_normal((57, hl, wl)).astype(np.float32)
+    pad, padded = [0, 0, pad_down, pad_right], (8 * hl, 8 * wl)
+    Hs, Ws = padded[0] - pad_down, padded[1] - pad_right
+    heat = np.zeros((H, W, 19)) + upsample_map(maps[38:], pad, padded, (H, W)) / 1
+    mid = resize_cubic(np.ascontiguousarray(np.transpose(maps[:38], (1, 2, 0))), (0, 0), fx=8, fy=8)[:Hs, :Ws]
+    return maps, np.transpose(heat[:, :, :18], (2, 0, 1)), np.transpose(mid, (2, 0, 1))
+
+
+@pytest.mark.parametrize("case", HEAT_BUCKETS, ids=lambda c: "x".join(str(v) for v in c))
+def test_heat_resize_buckets_bit_exact(native, handle, case):
+    hl, wl, pad_down, pad_right, H, W = case
+    maps, ref_heat, ref_mid = heat_bucket_case(case)
+    heat = np.empty((18, H, W), np.float64)
+    paf_mid = np.empty(ref_mid.shape, np.float32)
+    handle.check(native.lib.opose_debug_heat(handle.h, maps.ctypes.data, hl, wl, pad_down, pad_right, H, W,
+                                             heat.ctypes.data, paf_mid.ctypes.data))
+    assert np.array_equal(heat, ref_heat)
+    assert np.array_equal(paf_mid, ref_mid)
+
+
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "body_planted_*.npz"))),
                          ids=os.path.basename)
 def test_body_post_matches_reference_exactly(body, path):
