@@ -16,6 +16,10 @@
  *   Body.__call__ after the net    src/body.py:52-212        opose_body_post   (parity entry point)
  *   Hand.__call__                  src/hand.py:25-75         opose_hand_infer
  *   Hand.__call__ after the net    src/hand.py:51-75         opose_hand_post   (parity entry point)
+ *   HandImageDataset.__getitem__   srcmx/Batch_model.py:     opose_batch_hand_boxes (+ utilmx.handDetect),
+ *                                  69-104                    opose_batch_hand_crops (parity entry point)
+ *   Batch_hand_extraction's loop   srcmx/Batch_motion_       opose_batch_hand_extract
+ *                                  Estimation.py:19-65
  *   one scale of Body.__call__     src/body.py:36-50         opose_body_scale_maps; its output rows
  *                                                            opose_body_band_maps (C5 split)
  *
@@ -252,6 +256,40 @@ int opose_batch_hand_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, 
  * network outputs; peaks in the (8 hl) x (8 wl) frame. */
 int opose_batch_hand_post(opose_t* h, const float* maps, int N, int hl, int wl, const opose_params* p,
                           double* peaks, int32_t* found, int flags);
+
+/* ---- fast-mode hand extraction (srcmx/Batch_motion_Estimation.py:19-65 Batch_hand_extraction) -- */
+/* Slots: every frame has two, left then right; slot = 2 * frame + side.  A box is int32
+ * {x, y, w, present}: the square frame[y:y+w, x:x+w] utilmx.handDetect gives for that side, all
+ * zeros when the side's shoulder, elbow or wrist is missing from the pose.  boxsize must be a
+ * positive multiple of 8 (else OPOSE_E_ARG).  With OPOSE_IN_DEVICE the inputs (bgr, motion,
+ * boxes) are device memory; with OPOSE_OUT_DEVICE the outputs are, and the call is asynchronous
+ * on the handle's stream (it then returns OPOSE_OK: the per-slot status is the caller's to read).
+ * A region of interest of larger frames is a pointer offset plus the frames' row_stride. */
+
+/* HandImageDataset.__getitem__'s subset construction + utilmx.handDetect (srcmx/Batch_model.py:
+ * 74-84, srcmx/utilmx.py:267-327) for N poses motion [N][18][3] (x, y, score; a joint whose three
+ * values sum to 0 is missing) in H x W frames: boxes [N][2][4]. */
+int opose_batch_hand_boxes(opose_t* h, const double* motion, int N, int H, int W, int32_t* boxes, int flags);
+
+/* The crops HandImageDataset cuts (srcmx/Batch_model.py:86-99) as uint8 BGR
+ * [N][2][boxsize][boxsize][3]: cv2.resize(INTER_CUBIC) of each box, the left hand's mirrored first
+ * (cv2.flip(.., 1)); an absent slot is gray (128).  A present box with w < 1 or outside the frame
+ * reads nothing, is written gray and makes the call return OPOSE_E_SHAPE (the reference dies in
+ * cv2.resize there).  Parity entry point: opose_batch_hand_extract builds the network input in the
+ * same kernel without the uint8 intermediate. */
+int opose_batch_hand_crops(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                           int64_t frame_stride, const int32_t* boxes, int boxsize, uint8_t* crops, int flags);
+
+/* N frames + their N body poses -> HandMat rows handmat [N][42][3] (left hand rows 0..20, right
+ * 21..41; x, y in frame pixels, score; a missing part is 0, 0, 0): boxes, crops, the hand network
+ * and Batch_hand's post-processing (p as opose_batch_hand_infer: p->thre_hand) on all 2N crops,
+ * and the loop body of Batch_hand_extraction (srcmx/Batch_motion_Estimation.py:44-58), with no
+ * host round trip in between.  An absent hand's positions are 0 and its scores whatever the
+ * network finds on the gray crop, as the reference stores them.  status [N][2]: OPOSE_OK, or
+ * OPOSE_E_SHAPE for a present box that is empty (see opose_batch_hand_crops); returns the worst. */
+int opose_batch_hand_extract(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                             int64_t frame_stride, const double* motion, int boxsize, const opose_params* p,
+                             double* handmat, int32_t* status, int flags);
 
 /* Hand on N crops uint8 [H][W][3] (util.handDetect gives squares): peaks [N][21][3]
  * (x, y, score), found [N][21] (0 = part missing, the reference's [0,0,0] row). */

@@ -384,6 +384,16 @@ struct opose_ctx {
     std::vector<std::vector<int>> sched_host;  // sources of the asynchronous uploads
     opose::DevBuf frames, mids[2][opose::kMaxScales], avg, cnt, list, peak_pos, part_cnt, score, conn, conn_cnt, records, maps_in,
         hlab, hsums, hpeaks, hfound, list_score, hsel;
+    // fast-mode hand extraction (opose_batch_hand_boxes / _crops / _extract): staged poses, the
+    // boxes and per-slot status, staged results
+    opose::DevBuf hx_motion, hx_boxes, hx_status, hx_crops, hx_handmat;
+    // opose_batch_hand_extract cuts its 2N crops into chunks the conv kernels can address (as
+    // opose_hand_infer_crops does); OPOSE_EXTRACT_CHUNK=n at handle creation: n crops per chunk
+    // instead (tests/test_gpu_hand_extract.py runs a small batch in two chunks)
+    int extract_chunk = [] {
+        const char* e = getenv("OPOSE_EXTRACT_CHUNK");
+        return e ? std::atoi(e) : 0;
+    }();
     opose::PinnedBuf hand_out;  // Hand() peaks + found, staged for the host
     // network workspace, one set per concurrently running scale (slot s runs on scale_stream(s);
     // slot 0 is the handle's stream): input, activations, k-slab partials

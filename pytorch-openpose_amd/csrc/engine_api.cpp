@@ -661,6 +661,138 @@ int opose_batch_hand_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, 
     return OPOSE_OK;
 }
 
+// ---- fast-mode hand extraction (srcmx/Batch_model.py:55-104, srcmx/utilmx.py:267-327,
+// srcmx/Batch_motion_Estimation.py:19-65) -------------------------------------------------------
+// grid z runs over the 2N slots of a batch
+static bool extract_batch_ok(int N, int boxsize) { return N > 0 && N <= 32767 && boxsize > 0 && boxsize % 8 == 0; }
+
+// n values of T on the device: the caller's pointer (in_device), or the copy of the host values in buf
+template <class T>
+static const T* stage_values(opose_ctx* h, DevBuf& buf, const T* v, size_t n, bool in_device) {
+    if (in_device) return v;
+    T* d = buf.ensure<T>(n, h->stream);
+    OPOSE_HIP_CHECK(hipMemcpyAsync(d, v, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    return d;
+}
+
+// the worst of n per-slot statuses on the device, once the handle's stream has passed them
+static int worst_slot_status(opose_ctx* h, const int32_t* status_dev, int n, int32_t* status_out) {
+    std::vector<int32_t> st(n);
+    OPOSE_HIP_CHECK(hipMemcpyAsync(st.data(), status_dev, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
+    OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (status_out) std::memcpy(status_out, st.data(), sizeof(int32_t) * n);
+    return *std::min_element(st.begin(), st.end());
+}
+
+static void run_hand_boxes(opose_ctx* h, const double* motion_dev, int N, int H, int W, int32_t* boxes_dev) {
+    ProfEntry pe;
+    h->prof_begin(pe, "hand_boxes", 0, (double)N * (18 * 24 + 32));
+    launch_hand_boxes(motion_dev, N, H, W, boxes_dev, h->stream);
+    h->prof_end(pe);
+}
+
+static void run_hand_crops(opose_ctx* h, const uint8_t* fd, int64_t frame_stride, int64_t row_stride, int N, int H,
+                           int W, const int32_t* boxes_dev, int bs, float* x, uint8_t* crops, int32_t* status_dev) {
+    ProfEntry pe;
+    h->prof_begin(pe, "hand_crops", 0, 2.0 * N * bs * bs * ((x ? 12.0 : 0.0) + (crops ? 3.0 : 0.0)));
+    launch_hand_crops(fd, frame_stride, row_stride, N, H, W, boxes_dev, bs, x, crops, status_dev, h->stream);
+    h->prof_end(pe);
+}
+
+int opose_batch_hand_boxes(opose_t* h, const double* motion, int N, int H, int W, int32_t* boxes, int flags) {
+    if (!h || !motion || !boxes || H <= 0 || W <= 0 || !extract_batch_ok(N, 8)) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const double* md = stage_values(h, h->hx_motion, motion, (size_t)N * 54, flags & OPOSE_IN_DEVICE);
+        const bool od = flags & OPOSE_OUT_DEVICE;
+        int32_t* bd = od ? boxes : h->hx_boxes.ensure<int32_t>((size_t)N * 8, h->stream);
+        run_hand_boxes(h, md, N, H, W, bd);
+        if (!od) {
+            OPOSE_HIP_CHECK(hipMemcpyAsync(boxes, bd, sizeof(int32_t) * N * 8, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_batch_hand_crops(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                           int64_t frame_stride, const int32_t* boxes, int boxsize, uint8_t* crops, int flags) {
+    if (!h || !bgr || !boxes || !crops || H <= 0 || W <= 0 || !extract_batch_ok(N, boxsize)) return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, flags);
+        const int32_t* bd = stage_values(h, h->hx_boxes, boxes, (size_t)N * 8, flags & OPOSE_IN_DEVICE);
+        const bool od = flags & OPOSE_OUT_DEVICE;
+        const size_t bytes = (size_t)2 * N * boxsize * boxsize * 3;
+        uint8_t* cd = od ? crops : h->hx_crops.ensure<uint8_t>(bytes, h->stream);
+        int32_t* sd = h->hx_status.ensure<int32_t>((size_t)2 * N, h->stream);
+        run_hand_crops(h, fd, frame_stride, row_stride, N, H, W, bd, boxsize, nullptr, cd, sd);
+        if (od) {
+            h->prof_drain();
+            return OPOSE_OK;
+        }
+        OPOSE_HIP_CHECK(hipMemcpyAsync(crops, cd, bytes, hipMemcpyDeviceToHost, h->stream));
+        const int worst = worst_slot_status(h, sd, 2 * N, nullptr);
+        h->prof_drain();
+        if (worst != OPOSE_OK) h->err = "a present hand box is empty or leaves the frame";
+        return worst;
+    });
+}
+
+int opose_batch_hand_extract(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                             int64_t frame_stride, const double* motion, int boxsize, const opose_params* pp,
+                             double* handmat, int32_t* status, int flags) {
+    if (!h || !bgr || !motion || !handmat || !status || H <= 0 || W <= 0 || !extract_batch_ok(N, boxsize))
+        return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const opose_params p = fill_params(pp, OPOSE_NET_HAND);
+        const int bs = boxsize, slots = 2 * N;
+        const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, flags);
+        const double* md = stage_values(h, h->hx_motion, motion, (size_t)N * 54, flags & OPOSE_IN_DEVICE);
+        const bool od = flags & OPOSE_OUT_DEVICE;
+        // every buffer that outlives a chunk is sized here, before the first chunk: a reallocation
+        // later would drop the results of the crops already done.  (The network's and the
+        // post-processing's workspace is sized by the first chunk, the largest.)
+        int32_t* bd = h->hx_boxes.ensure<int32_t>((size_t)slots * 4, h->stream);
+        int32_t* sd = od ? status : h->hx_status.ensure<int32_t>((size_t)slots, h->stream);
+        double* hm = od ? handmat : h->hx_handmat.ensure<double>((size_t)N * 126, h->stream);
+        double* peaks = h->hpeaks.ensure<double>((size_t)slots * 63, h->stream);
+        int32_t* found = h->hfound.ensure<int>((size_t)slots * 21, h->stream);
+        const size_t per_crop = (size_t)3 * bs * bs;
+        float* x = h->w().x.ensure<float>((size_t)slots * per_crop, h->stream);
+        run_hand_boxes(h, md, N, H, W, bd);
+        run_hand_crops(h, fd, frame_stride, row_stride, N, H, W, bd, bs, x, nullptr, sd);
+        // chunks as opose_hand_infer_crops cuts them: the largest activation (64 channels at full
+        // resolution, X6: 3 x 128 B per pixel) stays below the 2 GiB the conv kernels address
+        // with 32-bit offsets
+        const int fit = (int)std::max<size_t>(1, (((size_t)1 << 31) - 1) / ((size_t)3 * 128 * bs * bs));
+        const int chunk = h->extract_chunk > 0 ? std::min(h->extract_chunk, fit) : fit;
+        for (int c0 = 0; c0 < slots; c0 += chunk) {
+            const int nc = std::min(chunk, slots - c0);
+            float* Sb = hand_net(h, x + (size_t)c0 * per_crop, nc, bs, bs);
+            batch_hand_post_common(h, nc, bs, bs, Sb, 150, p, peaks + (size_t)c0 * 63, found + (size_t)c0 * 21,
+                                   OPOSE_OUT_DEVICE);
+        }
+        ProfEntry pe;
+        h->prof_begin(pe, "hand_backmap", 0, (double)slots * 21 * 52);
+        launch_hand_backmap(peaks, found, bd, N, bs, hm, h->stream);
+        h->prof_end(pe);
+        if (od) {
+            h->prof_drain();
+            return OPOSE_OK;
+        }
+        OPOSE_HIP_CHECK(hipMemcpyAsync(handmat, hm, sizeof(double) * N * 126, hipMemcpyDeviceToHost, h->stream));
+        const int worst = worst_slot_status(h, sd, slots, status);
+        h->prof_drain();
+        if (worst != OPOSE_OK) h->err = "a present hand box is empty or leaves the frame";
+        return worst;
+    });
+}
+
 int opose_hand_infer_crops(opose_t* h, const uint8_t* const* crops, const int* sizes, const int64_t* row_strides,
                            int n, const opose_params* pp, double* peaks, int32_t* found, int flags) {
     if (!h || !crops || !sizes || !row_strides || !peaks || !found || n <= 0) return OPOSE_E_ARG;

@@ -123,6 +123,14 @@ void launch_upsample8_torch(const float* in, int in_cstride, int in_coff, int C,
 void launch_resize_torch_f32(const float* mid, int Cm, int coff, int P, int N, int nh, int nw, int H, int W,
                              float* out, hipStream_t st);
 
+// handcrop.hip: the fast mode's hand extraction (boxes [N][2][4] = {x, y, w, present}, slot =
+// 2 * frame + side, left then right)
+void launch_hand_boxes(const double* motion, int N, int H, int W, int32_t* boxes, hipStream_t st);
+void launch_hand_crops(const uint8_t* src, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
+                       const int32_t* boxes, int bs, float* x, uint8_t* crops, int32_t* status, hipStream_t st);
+void launch_hand_backmap(const double* peaks, const int32_t* found, const int32_t* boxes, int N, int bs,
+                         double* handmat, hipStream_t st);
+
 // post.hip
 void launch_gauss_nms(const void* avg, bool f32, int NP, int H, int W, double thre, int cap, int* cnt, int* list,
                       double* list_score, hipStream_t st);

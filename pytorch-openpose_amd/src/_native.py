@@ -74,6 +74,9 @@ def _load():
         "opose_batch_body_post": (I, [P, P, I, I, I, I, I, I, I, C.POINTER(Params), P, I]),
         "opose_batch_hand_infer": (I, [P, P, I, I, I, C.c_int64, C.c_int64, C.POINTER(Params), P, P, I]),
         "opose_batch_hand_post": (I, [P, P, I, I, I, C.POINTER(Params), P, P, I]),
+        "opose_batch_hand_boxes": (I, [P, P, I, I, I, P, I]),
+        "opose_batch_hand_crops": (I, [P, P, I, I, I, C.c_int64, C.c_int64, P, I, P, I]),
+        "opose_batch_hand_extract": (I, [P, P, I, I, I, C.c_int64, C.c_int64, P, I, C.POINTER(Params), P, P, I]),
         "opose_profile_enable": (I, [P, I]),
         "opose_profile_reset": (I, [P]),
         "opose_profile_read": (I, [P, C.c_char_p, S]),
@@ -103,7 +106,8 @@ EXPORTED = ["opose_default_params", "opose_create", "opose_destroy", "opose_last
             "opose_load_weights", "opose_body_forward", "opose_hand_forward", "opose_hand_forward_pyramid",
             "opose_body_infer",
             "opose_body_post", "opose_body_scale_geom", "opose_body_scale_maps",
-            "opose_body_post_scales", "opose_body_band_halo_bytes", "opose_body_band_maps", "opose_rccl_unique_id", "opose_rccl_init", "opose_rccl_abort", "opose_rccl_wait", "opose_set_band_peers", "opose_batch_body_infer", "opose_batch_body_post", "opose_batch_hand_infer", "opose_batch_hand_post", "opose_hand_infer", "opose_hand_infer_crops", "opose_hand_post", "opose_profile_enable",
+            "opose_body_post_scales", "opose_body_band_halo_bytes", "opose_body_band_maps", "opose_rccl_unique_id", "opose_rccl_init", "opose_rccl_abort", "opose_rccl_wait", "opose_set_band_peers", "opose_batch_body_infer", "opose_batch_body_post", "opose_batch_hand_infer", "opose_batch_hand_post",
+            "opose_batch_hand_boxes", "opose_batch_hand_crops", "opose_batch_hand_extract", "opose_hand_infer", "opose_hand_infer_crops", "opose_hand_post", "opose_profile_enable",
             "opose_profile_reset", "opose_profile_read", "opose_debug_conv", "opose_debug_conv_time", "opose_debug_conv_x6", "opose_debug_conv_x6_time", "opose_debug_preprocess",
             "opose_debug_heat", "opose_debug_hand_label"]
 

@@ -107,7 +107,10 @@ class Batch_body(Body):
 class Batch_hand(object):
     """srcmx/Batch_model.py:310-354: crops already resized to boxsize (the data loader's
     HandImageDataset does that with cv2) -> np.array [B, 21, 3] of (x, y, score) in crop
-    pixels, float64 (int64 when nothing is found anywhere, as np.array of [0, 0, 0] rows)."""
+    pixels, float64 (int64 when nothing is found anywhere, as np.array of [0, 0, 0] rows).
+
+    The stage that feeds it in the reference (the data loader's boxes, flips and cv2 resizes) and
+    the back-mapping that follows it run on the device too: `boxes`, `crops`, `extract`."""
 
     def __init__(self, model_path, device: int = 0, thre=0.035):
         from .hand import _load_state
@@ -139,6 +142,114 @@ class Batch_hand(object):
         self.handle.check(_native.lib.opose_batch_hand_post(self.handle.h, heat.ctypes.data, N, hl, wl, self.params,
                                                             peaks.ctypes.data, found.ctypes.data, 0))
         return self._as_reference(peaks, found)
+
+    # ---- hand extraction: HandImageDataset (srcmx/Batch_model.py:55-104) and the loop body of
+    # Batch_hand_extraction (srcmx/Batch_motion_Estimation.py:29-60) on the device
+    @staticmethod
+    def _frames_view(frames, recpoint):
+        """frames [N, H, W, 3] uint8 (numpy, or a torch CUDA tensor) cut to recpoint
+        [(x0, y0), (x1, y1)] without a copy: (view, N, H, W, row_stride, frame_stride, on_device).
+        The view keeps the frames' strides: the region of interest is a pointer offset."""
+        dev = hasattr(frames, "data_ptr")
+        if not dev:
+            frames = np.asarray(frames)
+        if frames.ndim != 4 or frames.shape[3] != 3 or str(frames.dtype).split(".")[-1] != "uint8":
+            raise ValueError("expected uint8 frames [N, H, W, 3]")
+        v = frames if recpoint is None else frames[:, recpoint[0][1]:recpoint[1][1], recpoint[0][0]:recpoint[1][0], :]
+        N, H, W, _ = v.shape
+        if N < 1 or H < 1 or W < 1:
+            raise ValueError("no frames, or an empty region of interest")
+        for _ in range(2):
+            st = v.stride() if dev else v.strides
+            row_stride = st[1] if H > 1 else 3 * W  # size-1 axes: any stride
+            frame_stride = st[0] if N > 1 else row_stride * H
+            if st[3] == 1 and st[2] == 3 and row_stride >= 3 * W and frame_stride >= row_stride * H:
+                break
+            v = v.contiguous() if dev else np.ascontiguousarray(v)
+        return v, N, H, W, int(row_stride), int(frame_stride), dev
+
+    @staticmethod
+    def _motion(motion, N):
+        motion = np.ascontiguousarray(motion, dtype=np.float64)
+        if motion.shape != (N, 18, 3):
+            raise ValueError("expected one body pose [18, 3] per frame: motion [%d, 18, 3]" % N)
+        return motion
+
+    def boxes(self, motion, hw):
+        """HandImageDataset's utilmx.handDetect call (srcmx/Batch_model.py:74-84) for N poses
+        motion [N, 18, 3] in frames of hw = (H, W): int32 [N, 2, 4] = {x, y, w, present}, left
+        then right; an absent side is zeros."""
+        motion = self._motion(motion, len(motion))
+        boxes = np.empty((len(motion), 2, 4), np.int32)
+        self.handle.check(_native.lib.opose_batch_hand_boxes(self.handle.h, motion.ctypes.data, len(motion),
+                                                             int(hw[0]), int(hw[1]), boxes.ctypes.data, 0))
+        return boxes
+
+    @staticmethod
+    def _raise_empty(bad):
+        n, side = (int(i) for i in np.argwhere(bad)[0])
+        raise ValueError("frame %d: the %s hand's box is empty (cv2.resize of an empty crop in the reference)"
+                         % (n, ("left", "right")[side]))
+
+    def crops(self, frames, motion, boxsize=368, recpoint=None):
+        """The crops HandImageDataset cuts (srcmx/Batch_model.py:86-99): uint8
+        [N, 2, boxsize, boxsize, 3], left (mirrored) then right, gray 128 where a hand is absent."""
+        v, N, H, W, rs, fs, dev = self._frames_view(frames, recpoint)
+        boxes = self.boxes(motion, (H, W))
+        out = np.empty((N, 2, int(boxsize), int(boxsize), 3), np.uint8)
+        flags = 0
+        if dev:
+            import torch
+            boxes_in = torch.from_numpy(boxes).to(v.device)
+            self.handle.wait_torch()
+            flags = _native.IN_DEVICE
+        else:
+            boxes_in = boxes
+        rc = _native.lib.opose_batch_hand_crops(self.handle.h, _native._ptr(v), N, H, W, rs, fs, _native._ptr(boxes_in),
+                                                int(boxsize), out.ctypes.data, flags)
+        if dev:
+            self.handle.signal_torch()
+        if rc == _native.OPOSE_E_SHAPE and ((boxes[:, :, 3] != 0) & (boxes[:, :, 2] < 1)).any():
+            self._raise_empty((boxes[:, :, 3] != 0) & (boxes[:, :, 2] < 1))
+        self.handle.check(rc)
+        return out
+
+    def extract_status(self, frames, motion, boxsize=368, recpoint=None):
+        """extract() without its check: (HandMat rows float64 [N, 42, 3], status int32 [N, 2]), a
+        slot's status OPOSE_E_SHAPE where a present hand's box is empty."""
+        v, N, H, W, rs, fs, dev = self._frames_view(frames, recpoint)
+        motion = self._motion(motion, N)
+        if dev:
+            import torch
+            m = torch.from_numpy(motion).to(v.device)
+            handmat = torch.empty((N, 42, 3), dtype=torch.float64, device=v.device)
+            status = torch.empty((N, 2), dtype=torch.int32, device=v.device)
+            self.handle.wait_torch()
+            self.handle.check(_native.lib.opose_batch_hand_extract(
+                self.handle.h, v.data_ptr(), N, H, W, rs, fs, m.data_ptr(), int(boxsize), self.params,
+                handmat.data_ptr(), status.data_ptr(), _native.IN_DEVICE | _native.OUT_DEVICE))
+            self.handle.signal_torch()
+            return handmat.cpu().numpy(), status.cpu().numpy()
+        handmat = np.empty((N, 42, 3), np.float64)
+        status = np.empty((N, 2), np.int32)
+        rc = _native.lib.opose_batch_hand_extract(self.handle.h, v.ctypes.data, N, H, W, rs, fs, motion.ctypes.data,
+                                                  int(boxsize), self.params, handmat.ctypes.data, status.ctypes.data, 0)
+        if rc != _native.OPOSE_E_SHAPE:
+            self.handle.check(rc)
+        return handmat, status
+
+    def extract(self, frames, motion, boxsize=368, recpoint=None):
+        """N frames (numpy [N, H, W, 3] uint8, or a torch CUDA uint8 tensor) and their body poses
+        motion [N, 18, 3] -> HandMat rows float64 [N, 42, 3]: rows 0..20 the left hand, 21..41 the
+        right, (x, y) in the pixels of the frame cut to recpoint [(x0, y0), (x1, y1)], score.  One
+        launch sequence on the device: boxes, crops, the hand network, Batch_hand's
+        post-processing, the back-mapping of Batch_hand_extraction's loop."""
+        handmat, status = self.extract_status(frames, motion, boxsize, recpoint)
+        if (status == _native.OPOSE_E_SHAPE).any():
+            self._raise_empty(status == _native.OPOSE_E_SHAPE)
+        if (status != 0).any():
+            raise _native.OposeError(int(status.min()), "hand extraction failed")
+        return handmat
 
     @staticmethod
     def _as_reference(peaks, found):

@@ -222,6 +222,39 @@ def extract_motion_data(frames, body, hand=None, outpath=None, recpoint=None, mo
     return motion
 
 
+def Batch_hand_extraction(videopath, motiondata, recpoints, outpath, *, hand, batch=32, capture=None):
+    """The reference's fast-mode hand pass (srcmx/Batch_motion_Estimation.py:19-65) on the GPU:
+    the video's frames and the body MotionMat [T, 18, 3] of a first pass -> HandMat [T, 42, 3]
+    (left hand rows 0..20, right 21..41), written to `outpath` with joblib.dump.  Returns None,
+    like the reference.  AssertionError unless the container reports len(motiondata) frames
+    (HandImageDataset, srcmx/Batch_model.py:63-64).  hand: a src.batch_model.Batch_hand (the
+    reference's module-level batch_hand_estimation); each batch of frames is one Batch_hand.extract
+    at the reference's boxsize 368, the region of interest recpoints [(x0, y0), (x1, y1)] applied
+    as an offset into the whole frames.  capture: see VideoFrames."""
+    import itertools
+    boxsize = 368
+    video = VideoFrames(videopath, capture=capture)
+    FrameCounts = len(video)
+    assert FrameCounts == len(motiondata)
+    motiondata = np.asarray(motiondata, dtype=np.float64)
+    COUNTS = len(motiondata)
+    HandMat = np.zeros((COUNTS, 42, 3))
+    count = 0
+    for frames in _batches(itertools.islice(video, COUNTS), None, batch):
+        n = len(frames)
+        HandMat[count:count + n] = hand.extract(np.stack(frames), motiondata[count:count + n], boxsize, recpoints)
+        for c in range(count + 1, count + n + 1):
+            if c % 1000 == 0:
+                print('%s-%d/%d' % (outpath, c, COUNTS))
+        count += n
+    if count < COUNTS:  # the reference slices the None a failed read returns (srcmx/Batch_model.py:70-71)
+        raise TypeError("'NoneType' object is not subscriptable")
+    import joblib
+    joblib.dump(HandMat, outpath)
+    print('the %s file is saved' % outpath)
+    return None
+
+
 def Extract_MotionData_from_Video(videopath, outpath, Recpoint, mode="body", overwrite=False, *, body, hand=None,
                                   batch=32, device=None, capture=None):
     """The reference's entry point (srcmx/MotionEstimation.py:25-76) on the GPU Body / Hand:

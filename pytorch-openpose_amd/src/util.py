@@ -36,9 +36,16 @@ def transfer(model, model_weights):
 
 def handDetect(candidate, subset, oriImg):
     """Hand boxes [x, y, w, is_left] (ints) from shoulder/elbow/wrist (src/util.py:133-201)."""
+    return handDetect_shape(candidate, subset, oriImg.shape[0:2])
+
+
+def handDetect_shape(candidate, subset, img_shape):
+    """utilmx.handDetect (srcmx/utilmx.py:267-327): handDetect for an image given by its
+    (height, width) only, as the fast mode's HandImageDataset calls it.  On the device:
+    Batch_hand.boxes."""
     ratio = 0.33
     out = []
-    img_h, img_w = oriImg.shape[0:2]
+    img_h, img_w = img_shape
     for person in subset.astype(int):
         arms = []
         if np.sum(person[[5, 6, 7]] == -1) == 0:
