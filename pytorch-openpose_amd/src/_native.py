@@ -18,6 +18,7 @@ OPOSE_E_ARG, OPOSE_E_SHAPE, OPOSE_E_HIP, OPOSE_E_WEIGHTS, OPOSE_E_CAPACITY, OPOS
 OPOSE_E_TIMEOUT = -7
 NET_BODY, NET_HAND = 0, 1
 IN_DEVICE, OUT_DEVICE, PIPELINE, PIPELINE_DEFER = 1, 2, 4, 8
+DEVICE_IO = IN_DEVICE | OUT_DEVICE
 MAX_SCALES = 8
 
 
@@ -31,85 +32,77 @@ class Params(C.Structure):
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
+_P, _I, _L, _D, _S = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t
+# name -> (restype, argtypes) of every symbol include/opose.h declares
+SIGNATURES = {
+    "opose_default_params": (None, [_I, C.POINTER(Params)]),
+    "opose_create": (_I, [_I, C.POINTER(_P)]),
+    "opose_destroy": (None, [_P]),
+    "opose_last_error": (C.c_char_p, [_P]),
+    "opose_set_stream": (_I, [_P, _P]),
+    "opose_wait_stream": (_I, [_P, _P]),
+    "opose_signal_stream": (_I, [_P, _P]),
+    "opose_signal_input": (_I, [_P, _P]),
+    "opose_get_stream": (_P, [_P]),
+    "opose_synchronize": (_I, [_P]),
+    "opose_flush": (_I, [_P]),
+    "opose_set_capacity": (_I, [_P, _I, _I]),
+    "opose_body_record_bytes": (_S, [_P]),
+    "opose_load_weights": (_I, [_P, _I, C.POINTER(_P), _P, _I]),
+    "opose_body_forward": (_I, [_P, _P, _I, _I, _I, _P, _P, _I]),
+    "opose_hand_forward": (_I, [_P, _P, _I, _I, _I, _P, _I]),
+    "opose_hand_forward_pyramid": (_I, [_P, _I, C.POINTER(_P), _P, _P, _P, C.POINTER(_P), _I]),
+    "opose_body_infer": (_I, [_P, _P, _I, _I, _I, _L, _L, C.POINTER(Params), _P, _I]),
+    "opose_body_post": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(Params), _P, _I]),
+    "opose_body_scale_geom": (_I, [_I, _I, C.POINTER(Params), _I, _P]),
+    "opose_body_scale_maps": (_I, [_P, _P, _I, _I, _I, _L, _L, C.POINTER(Params), _I, _P, _I]),
+    "opose_body_post_scales": (_I, [_P, C.POINTER(_P), _P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(Params), _P, _I]),
+    "opose_body_band_halo_bytes": (_S, [_I]),
+    "opose_rccl_unique_id": (_I, [_P, _S]),
+    "opose_rccl_init": (_I, [_P, _P, _I, _I]),
+    "opose_rccl_abort": (_I, [_P]),
+    "opose_rccl_wait": (_I, [_P, _I]),
+    "opose_set_band_peers": (_I, [_P, _I, _I]),
+    "opose_body_band_maps": (_I, [_P, _P, _I, _I, _L, C.POINTER(Params), _I, _I, _I, _P, HALO_FN, _P, _P, _S, _I]),
+    "opose_hand_infer": (_I, [_P, _P, _I, _I, _I, _L, _L, C.POINTER(Params), _P, _P, _I]),
+    "opose_hand_post": (_I, [_P, C.POINTER(_P), _P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(Params), _P, _P, _I]),
+    "opose_hand_infer_crops": (_I, [_P, C.POINTER(_P), _P, _P, _I, C.POINTER(Params), _P, _P, _I]),
+    "opose_batch_body_infer": (_I, [_P, _P, _I, _I, _I, _L, _L, C.POINTER(Params), _P, _I]),
+    "opose_batch_body_post": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(Params), _P, _I]),
+    "opose_batch_hand_infer": (_I, [_P, _P, _I, _I, _I, _L, _L, C.POINTER(Params), _P, _P, _I]),
+    "opose_batch_hand_post": (_I, [_P, _P, _I, _I, _I, C.POINTER(Params), _P, _P, _I]),
+    "opose_batch_hand_boxes": (_I, [_P, _P, _I, _I, _I, _P, _I]),
+    "opose_batch_hand_crops": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _I, _P, _I]),
+    "opose_batch_hand_extract": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _I, C.POINTER(Params), _P, _P, _I]),
+    "opose_profile_enable": (_I, [_P, _I]),
+    "opose_profile_reset": (_I, [_P]),
+    "opose_profile_read": (_I, [_P, C.c_char_p, _S]),
+    "opose_debug_conv": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "opose_debug_preprocess": (_I, [_P, _P, _I, _I, _D, _I, _P, _P]),
+    "opose_debug_conv_time": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "opose_debug_conv_x6": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "opose_debug_conv_x6_time": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "opose_debug_heat": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "opose_debug_hand_label": (_I, [_P, _P, _I, _I, _I, _D, _P, _P]),
+}
+EXPORTED = list(SIGNATURES)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"libopose.so not found at {LIB_PATH}: build it with `make -C pytorch-openpose_amd` "
                           "(or __graft_entry__.build()); there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    P, I, D, S = C.c_void_p, C.c_int, C.c_double, C.c_size_t
-    sig = {
-        "opose_default_params": (None, [I, C.POINTER(Params)]),
-        "opose_create": (I, [I, C.POINTER(P)]),
-        "opose_destroy": (None, [P]),
-        "opose_last_error": (C.c_char_p, [P]),
-        "opose_set_stream": (I, [P, P]),
-        "opose_wait_stream": (I, [P, P]),
-        "opose_signal_stream": (I, [P, P]),
-        "opose_signal_input": (I, [P, P]),
-        "opose_get_stream": (P, [P]),
-        "opose_synchronize": (I, [P]),
-        "opose_flush": (I, [P]),
-        "opose_set_capacity": (I, [P, I, I]),
-        "opose_body_record_bytes": (S, [P]),
-        "opose_load_weights": (I, [P, I, C.POINTER(P), P, I]),
-        "opose_body_forward": (I, [P, P, I, I, I, P, P, I]),
-        "opose_hand_forward": (I, [P, P, I, I, I, P, I]),
-        "opose_hand_forward_pyramid": (I, [P, I, C.POINTER(P), P, P, P, C.POINTER(P), I]),
-        "opose_body_infer": (I, [P, P, I, I, I, C.c_int64, C.c_int64, C.POINTER(Params), P, I]),
-        "opose_body_post": (I, [P, P, I, I, I, I, I, I, I, C.POINTER(Params), P, I]),
-        "opose_body_scale_geom": (I, [I, I, C.POINTER(Params), I, P]),
-        "opose_body_scale_maps": (I, [P, P, I, I, I, C.c_int64, C.c_int64, C.POINTER(Params), I, P, I]),
-        "opose_body_post_scales": (I, [P, C.POINTER(P), P, P, P, P, I, I, I, I, C.POINTER(Params), P, I]),
-        "opose_body_band_halo_bytes": (S, [I]),
-        "opose_rccl_unique_id": (I, [P, S]),
-        "opose_rccl_init": (I, [P, P, I, I]),
-        "opose_rccl_abort": (I, [P]),
-        "opose_rccl_wait": (I, [P, I]),
-        "opose_set_band_peers": (I, [P, I, I]),
-        "opose_body_band_maps": (I, [P, P, I, I, C.c_int64, C.POINTER(Params), I, I, I, P, HALO_FN, P, P, S, I]),
-        "opose_hand_infer": (I, [P, P, I, I, I, C.c_int64, C.c_int64, C.POINTER(Params), P, P, I]),
-        "opose_hand_post": (I, [P, C.POINTER(P), P, P, P, P, I, I, I, I, C.POINTER(Params), P, P, I]),
-        "opose_hand_infer_crops": (I, [P, C.POINTER(P), P, P, I, C.POINTER(Params), P, P, I]),
-        "opose_batch_body_infer": (I, [P, P, I, I, I, C.c_int64, C.c_int64, C.POINTER(Params), P, I]),
-        "opose_batch_body_post": (I, [P, P, I, I, I, I, I, I, I, C.POINTER(Params), P, I]),
-        "opose_batch_hand_infer": (I, [P, P, I, I, I, C.c_int64, C.c_int64, C.POINTER(Params), P, P, I]),
-        "opose_batch_hand_post": (I, [P, P, I, I, I, C.POINTER(Params), P, P, I]),
-        "opose_batch_hand_boxes": (I, [P, P, I, I, I, P, I]),
-        "opose_batch_hand_crops": (I, [P, P, I, I, I, C.c_int64, C.c_int64, P, I, P, I]),
-        "opose_batch_hand_extract": (I, [P, P, I, I, I, C.c_int64, C.c_int64, P, I, C.POINTER(Params), P, P, I]),
-        "opose_profile_enable": (I, [P, I]),
-        "opose_profile_reset": (I, [P]),
-        "opose_profile_read": (I, [P, C.c_char_p, S]),
-        "opose_debug_conv": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P]),
-        "opose_debug_preprocess": (I, [P, P, I, I, D, I, P, P]),
-        "opose_debug_conv_time": (I, [P, I, I, I, I, I, I, I, I, I, I, I, I, P]),
-        "opose_debug_conv_x6": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P]),
-        "opose_debug_conv_x6_time": (I, [P, I, I, I, I, I, I, I, I, I, I, I, P]),
-        "opose_debug_heat": (I, [P, P, I, I, I, I, I, I, P, P]),
-        "opose_debug_hand_label": (I, [P, P, I, I, I, D, P, P]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in SIGNATURES.items():
         if "OPOSE_LIB" in os.environ and not hasattr(lib, name):
             continue  # an older build picked for a same-box A/B may predate later entry points
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    _ = D
     return lib
 
 
 lib = _load()
-
-EXPORTED = ["opose_default_params", "opose_create", "opose_destroy", "opose_last_error", "opose_set_stream",
-            "opose_wait_stream", "opose_signal_stream", "opose_signal_input",
-            "opose_get_stream", "opose_synchronize", "opose_flush", "opose_set_capacity", "opose_body_record_bytes",
-            "opose_load_weights", "opose_body_forward", "opose_hand_forward", "opose_hand_forward_pyramid",
-            "opose_body_infer",
-            "opose_body_post", "opose_body_scale_geom", "opose_body_scale_maps",
-            "opose_body_post_scales", "opose_body_band_halo_bytes", "opose_body_band_maps", "opose_rccl_unique_id", "opose_rccl_init", "opose_rccl_abort", "opose_rccl_wait", "opose_set_band_peers", "opose_batch_body_infer", "opose_batch_body_post", "opose_batch_hand_infer", "opose_batch_hand_post",
-            "opose_batch_hand_boxes", "opose_batch_hand_crops", "opose_batch_hand_extract", "opose_hand_infer", "opose_hand_infer_crops", "opose_hand_post", "opose_profile_enable",
-            "opose_profile_reset", "opose_profile_read", "opose_debug_conv", "opose_debug_conv_time", "opose_debug_conv_x6", "opose_debug_conv_x6_time", "opose_debug_preprocess",
-            "opose_debug_heat", "opose_debug_hand_label"]
 
 
 class OposeError(RuntimeError):
@@ -138,6 +131,34 @@ def _ptr(a) -> int:
     if isinstance(a, np.ndarray):
         return a.ctypes.data
     return int(a.data_ptr())  # torch tensor
+
+
+def frames_view(frames, what="frames"):
+    """uint8 [N, H, W, 3] frames (a numpy array or a torch tensor; what="crops": Hand's crops) as
+    every frame entry point of the library takes them:
+    (view, ptr, N, H, W, row_stride, frame_stride, on_device), strides in bytes.
+
+    The library wants packed BGR pixels, rows at least 3*W and frames at least row_stride*H apart.
+    A view that satisfies this is passed as it is (a region of interest stays a pointer offset);
+    any other (channels or rows reversed, a permuted [N,3,H,W], overlapping rows) is copied once.
+    A size-1 axis may carry any stride (0 for a numpy newaxis): it gets the dense one."""
+    dev = hasattr(frames, "data_ptr")
+    v = frames if dev else np.asarray(frames)
+    if v.ndim != 4 or v.shape[3] != 3 or (str(v.dtype) != "torch.uint8" if dev else v.dtype != np.uint8):
+        raise ValueError("expected uint8 crops [N, h, w, 3]" if what == "crops" else
+                         "expected uint8 frames [N, H, W, 3]")
+    N, H, W, _ = v.shape
+    if N < 1 or H < 1 or W < 1:
+        raise ValueError("no %s, or an empty region of interest" % what)
+    for copied in (False, True):
+        st = v.stride() if dev else v.strides
+        row_stride = st[1] if H > 1 else 3 * W
+        frame_stride = st[0] if N > 1 else row_stride * H
+        if st[3] == 1 and (st[2] == 3 or W == 1) and row_stride >= 3 * W and frame_stride >= row_stride * H:
+            return v, _ptr(v), N, H, W, int(row_stride), int(frame_stride), bool(dev and v.is_cuda)
+        if copied:
+            raise ValueError("%s with strides %s cannot be made dense" % (what, tuple(st)))
+        v = v.contiguous() if dev else np.ascontiguousarray(v)
 
 
 class Handle:
@@ -255,6 +276,13 @@ class Handle:
         complete for torch consumers and the inputs the handle read may be freed/reused."""
         self.check(lib.opose_signal_stream(self.h, self._torch_stream()))
 
+    def torch_call(self, fn, *args):
+        """check(fn(handle, *args)) between wait_torch and signal_torch: a call whose device
+        inputs come from torch's current stream and whose device outputs go back to it."""
+        self.wait_torch()
+        self.check(fn(self.h, *args))
+        self.signal_torch()
+
     def signal_input(self, stream=None):
         """Work queued on `stream` (a torch.cuda.Stream; default torch's current stream) from now on
         starts once the handle has read the device inputs of every call so far: after pipelined
@@ -329,3 +357,15 @@ def decode_record(rec: np.ndarray, peaks_per_part: int, max_people: int):
     if n_people == 0:
         sub = -1 * np.ones((0, 20))  # src/body.py:159
     return status, cand, sub
+
+
+def raise_record_status(status: int, peaks_per_part: int, max_people: int):
+    """A record's non-zero status as the exception the reference (or its absence of limits) means."""
+    if status == OPOSE_E_ASSEMBLY:
+        # the reference raises here when a third subset row matches (src/body.py:170-173)
+        raise IndexError("list assignment index out of range")
+    if status == OPOSE_E_CAPACITY:
+        raise RuntimeError("libopose: per-frame capacity exceeded (peaks_per_part=%d, max_people=%d)"
+                           % (peaks_per_part, max_people))
+    if status != 0:
+        raise OposeError(status, "frame failed")

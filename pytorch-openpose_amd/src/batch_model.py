@@ -21,7 +21,10 @@ from __future__ import annotations
 import numpy as np
 
 from . import _native
+from ._native import lib
 from .body import Body
+from .hand import _as_reference_array, hand_outputs
+from .model import handpose_model, load_model
 
 
 def size_pad(g_scale, height, width, boxsize=368, stride=8):
@@ -57,17 +60,9 @@ class Batch_body(Body):
         return self.batch(_as_uint8_frames(batch_images))
 
     def batch(self, frames):
-        frames = np.ascontiguousarray(frames)
-        N, H, W, _ = frames.shape
-        while True:
-            rec = np.empty((N, self.handle.record_bytes()), np.uint8)
-            rc = _native.lib.opose_batch_body_infer(self.handle.h, frames.ctypes.data, N, H, W, frames.strides[1],
-                                                    frames.strides[1] * H, self.params, rec.ctypes.data, 0)
-            if rc == _native.OPOSE_E_CAPACITY and self._grow():
-                continue
-            if rc not in (_native.OPOSE_OK, _native.OPOSE_E_CAPACITY, _native.OPOSE_E_ASSEMBLY):
-                self.handle.check(rc)
-            return [self._decode(r) for r in rec]
+        frames, ptr, N, H, W, rs, fs, _ = _native.frames_view(np.asarray(frames))
+        return self._records(N, lambda rec: lib.opose_batch_body_infer(self.handle.h, ptr, N, H, W, rs, fs,
+                                                                       self.params, rec, 0))
 
     def post(self, maps, H, W):
         """Post-network part only (srcmx/Batch_model.py:159-204): maps float32 [N, 57, hl, wl]
@@ -76,31 +71,17 @@ class Batch_body(Body):
         N, c, hl, wl = maps.shape
         assert c == 57
         _, nh, nw, _, _ = size_pad(self.scale_search, H, W, self.boxsize, self.stride)
-        while True:
-            rec = np.empty((N, self.handle.record_bytes()), np.uint8)
-            rc = _native.lib.opose_batch_body_post(self.handle.h, maps.ctypes.data, N, hl, wl, nh, nw, int(H), int(W),
-                                                   self.params, rec.ctypes.data, 0)
-            if rc == _native.OPOSE_E_CAPACITY and self._grow():
-                continue
-            if rc not in (_native.OPOSE_OK, _native.OPOSE_E_CAPACITY, _native.OPOSE_E_ASSEMBLY):
-                self.handle.check(rc)
-            return [self._decode(r) for r in rec]
+        return self._records(N, lambda rec: lib.opose_batch_body_post(self.handle.h, maps.ctypes.data, N, hl, wl, nh,
+                                                                      nw, int(H), int(W), self.params, rec, 0))
 
     def infer_records(self, frames_dev, records_dev=None):
         """Device-resident uint8 frames [N, H, W, 3] -> device records (asynchronous)."""
         import torch
-        N, H, W, _ = frames_dev.shape
-        if frames_dev.stride(3) != 1 or frames_dev.stride(2) != 3:
-            frames_dev = frames_dev.contiguous()
-        row_stride = frames_dev.stride(1) if H > 1 else 3 * W  # size-1 axes: any stride (numpy newaxis: 0)
-        frame_stride = frames_dev.stride(0) if N > 1 else row_stride * H
+        frames_dev, ptr, N, H, W, rs, fs, _ = _native.frames_view(frames_dev)
         if records_dev is None:
             records_dev = torch.empty((N, self.handle.record_bytes()), dtype=torch.uint8, device=frames_dev.device)
-        self.handle.wait_torch()
-        self.handle.check(_native.lib.opose_batch_body_infer(
-            self.handle.h, frames_dev.data_ptr(), N, H, W, row_stride, frame_stride, self.params,
-            records_dev.data_ptr(), _native.IN_DEVICE | _native.OUT_DEVICE))
-        self.handle.signal_torch()
+        self.handle.torch_call(lib.opose_batch_body_infer, ptr, N, H, W, rs, fs, self.params, records_dev.data_ptr(),
+                               _native.DEVICE_IO)
         return records_dev
 
 
@@ -113,60 +94,38 @@ class Batch_hand(object):
     the back-mapping that follows it run on the device too: `boxes`, `crops`, `extract`."""
 
     def __init__(self, model_path, device: int = 0, thre=0.035):
-        from .hand import _load_state
-        from .model import handpose_model
-        from . import util
-        self.model = handpose_model(device)
-        self.model.load_state_dict(util.transfer(self.model, _load_state(model_path)))
-        self.model.eval()
+        self.model = load_model(handpose_model, model_path, device)
         self.handle = self.model.handle
         self.params = _native.default_params(_native.NET_HAND, scale_search=(1.0,), thre_hand=float(thre))
 
     def __call__(self, batch_imgs):
-        crops = np.ascontiguousarray(_as_uint8_frames(batch_imgs))
-        N, H, W, _ = crops.shape
-        peaks = np.empty((N, 21, 3), np.float64)
-        found = np.empty((N, 21), np.int32)
-        self.handle.check(_native.lib.opose_batch_hand_infer(self.handle.h, crops.ctypes.data, N, H, W,
-                                                             crops.strides[1], crops.strides[1] * H, self.params,
-                                                             peaks.ctypes.data, found.ctypes.data, 0))
-        return self._as_reference(peaks, found)
+        crops, ptr, N, H, W, rs, fs, _ = _native.frames_view(_as_uint8_frames(batch_imgs))
+        peaks, found = hand_outputs(N)
+        self.handle.check(lib.opose_batch_hand_infer(self.handle.h, ptr, N, H, W, rs, fs, self.params,
+                                                     peaks.ctypes.data, found.ctypes.data, 0))
+        return _as_reference_array(peaks, found)
 
     def post(self, heat):
         """Post-network part only (srcmx/Batch_model.py:334-354): heat float32 [B, 22, hl, wl]."""
         heat = np.ascontiguousarray(heat, dtype=np.float32)
         N, c, hl, wl = heat.shape
         assert c == 22
-        peaks = np.empty((N, 21, 3), np.float64)
-        found = np.empty((N, 21), np.int32)
-        self.handle.check(_native.lib.opose_batch_hand_post(self.handle.h, heat.ctypes.data, N, hl, wl, self.params,
-                                                            peaks.ctypes.data, found.ctypes.data, 0))
-        return self._as_reference(peaks, found)
+        peaks, found = hand_outputs(N)
+        self.handle.check(lib.opose_batch_hand_post(self.handle.h, heat.ctypes.data, N, hl, wl, self.params,
+                                                    peaks.ctypes.data, found.ctypes.data, 0))
+        return _as_reference_array(peaks, found)
 
     # ---- hand extraction: HandImageDataset (srcmx/Batch_model.py:55-104) and the loop body of
     # Batch_hand_extraction (srcmx/Batch_motion_Estimation.py:29-60) on the device
     @staticmethod
     def _frames_view(frames, recpoint):
-        """frames [N, H, W, 3] uint8 (numpy, or a torch CUDA tensor) cut to recpoint
-        [(x0, y0), (x1, y1)] without a copy: (view, N, H, W, row_stride, frame_stride, on_device).
-        The view keeps the frames' strides: the region of interest is a pointer offset."""
-        dev = hasattr(frames, "data_ptr")
-        if not dev:
+        """_native.frames_view of frames [N, H, W, 3] uint8 (numpy, or a torch CUDA tensor) cut to
+        recpoint [(x0, y0), (x1, y1)]: the region of interest is a pointer offset, not a copy."""
+        if not hasattr(frames, "data_ptr"):
             frames = np.asarray(frames)
-        if frames.ndim != 4 or frames.shape[3] != 3 or str(frames.dtype).split(".")[-1] != "uint8":
-            raise ValueError("expected uint8 frames [N, H, W, 3]")
-        v = frames if recpoint is None else frames[:, recpoint[0][1]:recpoint[1][1], recpoint[0][0]:recpoint[1][0], :]
-        N, H, W, _ = v.shape
-        if N < 1 or H < 1 or W < 1:
-            raise ValueError("no frames, or an empty region of interest")
-        for _ in range(2):
-            st = v.stride() if dev else v.strides
-            row_stride = st[1] if H > 1 else 3 * W  # size-1 axes: any stride
-            frame_stride = st[0] if N > 1 else row_stride * H
-            if st[3] == 1 and st[2] == 3 and row_stride >= 3 * W and frame_stride >= row_stride * H:
-                break
-            v = v.contiguous() if dev else np.ascontiguousarray(v)
-        return v, N, H, W, int(row_stride), int(frame_stride), dev
+        if recpoint is not None and frames.ndim == 4:
+            frames = frames[:, recpoint[0][1]:recpoint[1][1], recpoint[0][0]:recpoint[1][0], :]
+        return _native.frames_view(frames)
 
     @staticmethod
     def _motion(motion, N):
@@ -181,8 +140,8 @@ class Batch_hand(object):
         then right; an absent side is zeros."""
         motion = self._motion(motion, len(motion))
         boxes = np.empty((len(motion), 2, 4), np.int32)
-        self.handle.check(_native.lib.opose_batch_hand_boxes(self.handle.h, motion.ctypes.data, len(motion),
-                                                             int(hw[0]), int(hw[1]), boxes.ctypes.data, 0))
+        self.handle.check(lib.opose_batch_hand_boxes(self.handle.h, motion.ctypes.data, len(motion), int(hw[0]),
+                                                     int(hw[1]), boxes.ctypes.data, 0))
         return boxes
 
     @staticmethod
@@ -194,20 +153,17 @@ class Batch_hand(object):
     def crops(self, frames, motion, boxsize=368, recpoint=None):
         """The crops HandImageDataset cuts (srcmx/Batch_model.py:86-99): uint8
         [N, 2, boxsize, boxsize, 3], left (mirrored) then right, gray 128 where a hand is absent."""
-        v, N, H, W, rs, fs, dev = self._frames_view(frames, recpoint)
+        v, ptr, N, H, W, rs, fs, dev = self._frames_view(frames, recpoint)
         boxes = self.boxes(motion, (H, W))
         out = np.empty((N, 2, int(boxsize), int(boxsize), 3), np.uint8)
-        flags = 0
+        boxes_in = boxes
         if dev:
             import torch
             boxes_in = torch.from_numpy(boxes).to(v.device)
             self.handle.wait_torch()
-            flags = _native.IN_DEVICE
-        else:
-            boxes_in = boxes
-        rc = _native.lib.opose_batch_hand_crops(self.handle.h, _native._ptr(v), N, H, W, rs, fs, _native._ptr(boxes_in),
-                                                int(boxsize), out.ctypes.data, flags)
-        if dev:
+        rc = lib.opose_batch_hand_crops(self.handle.h, ptr, N, H, W, rs, fs, _native._ptr(boxes_in), int(boxsize),
+                                        out.ctypes.data, _native.IN_DEVICE if dev else 0)
+        if dev:  # not Handle.torch_call: torch may reuse v and boxes_in whatever rc says, read below
             self.handle.signal_torch()
         if rc == _native.OPOSE_E_SHAPE and ((boxes[:, :, 3] != 0) & (boxes[:, :, 2] < 1)).any():
             self._raise_empty((boxes[:, :, 3] != 0) & (boxes[:, :, 2] < 1))
@@ -217,23 +173,20 @@ class Batch_hand(object):
     def extract_status(self, frames, motion, boxsize=368, recpoint=None):
         """extract() without its check: (HandMat rows float64 [N, 42, 3], status int32 [N, 2]), a
         slot's status OPOSE_E_SHAPE where a present hand's box is empty."""
-        v, N, H, W, rs, fs, dev = self._frames_view(frames, recpoint)
+        v, ptr, N, H, W, rs, fs, dev = self._frames_view(frames, recpoint)
         motion = self._motion(motion, N)
         if dev:
             import torch
             m = torch.from_numpy(motion).to(v.device)
             handmat = torch.empty((N, 42, 3), dtype=torch.float64, device=v.device)
             status = torch.empty((N, 2), dtype=torch.int32, device=v.device)
-            self.handle.wait_torch()
-            self.handle.check(_native.lib.opose_batch_hand_extract(
-                self.handle.h, v.data_ptr(), N, H, W, rs, fs, m.data_ptr(), int(boxsize), self.params,
-                handmat.data_ptr(), status.data_ptr(), _native.IN_DEVICE | _native.OUT_DEVICE))
-            self.handle.signal_torch()
+            self.handle.torch_call(lib.opose_batch_hand_extract, ptr, N, H, W, rs, fs, m.data_ptr(), int(boxsize),
+                                   self.params, handmat.data_ptr(), status.data_ptr(), _native.DEVICE_IO)
             return handmat.cpu().numpy(), status.cpu().numpy()
         handmat = np.empty((N, 42, 3), np.float64)
         status = np.empty((N, 2), np.int32)
-        rc = _native.lib.opose_batch_hand_extract(self.handle.h, v.ctypes.data, N, H, W, rs, fs, motion.ctypes.data,
-                                                  int(boxsize), self.params, handmat.ctypes.data, status.ctypes.data, 0)
+        rc = lib.opose_batch_hand_extract(self.handle.h, ptr, N, H, W, rs, fs, motion.ctypes.data, int(boxsize),
+                                          self.params, handmat.ctypes.data, status.ctypes.data, 0)
         if rc != _native.OPOSE_E_SHAPE:
             self.handle.check(rc)
         return handmat, status
@@ -250,10 +203,3 @@ class Batch_hand(object):
         if (status != 0).any():
             raise _native.OposeError(int(status.min()), "hand extraction failed")
         return handmat
-
-    @staticmethod
-    def _as_reference(peaks, found):
-        if not found.any():
-            return np.zeros(peaks.shape, dtype=np.int64)
-        peaks[~found.astype(bool)] = 0.0
-        return peaks

@@ -23,27 +23,22 @@ import ctypes
 
 import numpy as np
 
-from . import _native, util
-from .model import bodypose_model
+from . import _native
+from ._native import lib
+from .model import bodypose_model, load_model
 
 
-def _load_state(model_path):
-    if isinstance(model_path, dict):
-        return model_path
-    import torch
-    return torch.load(model_path, map_location="cpu", weights_only=True)
-
-
-ctypes_int4 = ctypes.c_int * 4
+def _as_batch(frames):
+    """[H, W, 3] -> [1, H, W, 3] (numpy array or torch tensor; anything else through numpy)."""
+    if not hasattr(frames, "data_ptr"):
+        frames = np.asarray(frames)
+    return frames[None] if frames.ndim == 3 else frames
 
 
 class Body(object):
     def __init__(self, model_path, device: int = 0, scale_search=(0.5,), boxsize=368, stride=8, padValue=128,
                  thre1=0.1, thre2=0.05, peaks_per_part=128, max_people=96):
-        self.model = bodypose_model(device)
-        model_dict = util.transfer(self.model, _load_state(model_path))
-        self.model.load_state_dict(model_dict)
-        self.model.eval()
+        self.model = load_model(bodypose_model, model_path, device)
         self.handle = self.model.handle
         self.params = _native.default_params(_native.NET_BODY, scale_search=scale_search, boxsize=float(boxsize),
                                              stride=int(stride), pad_value=int(padValue), thre1=float(thre1),
@@ -59,24 +54,9 @@ class Body(object):
         """frames: uint8 [N, H, W, 3] (or a list of equally sized frames) -> list of (candidate, subset)."""
         if isinstance(frames, (list, tuple)):
             frames = np.stack(frames)
-        frames = np.asarray(frames)
-        if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] != 3:
-            raise ValueError("expected uint8 frames [N, H, W, 3]")
-        if not (frames.strides[3] == 1 and frames.strides[2] == 3 and frames.strides[1] >= 3 * frames.shape[2]
-                and (frames.shape[0] == 1 or frames.strides[0] >= frames.strides[1] * frames.shape[1])):
-            frames = np.ascontiguousarray(frames)
-        N, H, W, _ = frames.shape
-        frame_stride = frames.strides[0] if N > 1 else frames.strides[1] * H
-        while True:
-            rb = self.handle.record_bytes()
-            rec = np.empty((N, rb), np.uint8)
-            rc = _native.lib.opose_body_infer(self.handle.h, frames.ctypes.data, N, H, W, frames.strides[1],
-                                              frame_stride, self.params, rec.ctypes.data, 0)
-            if rc == _native.OPOSE_E_CAPACITY and self._grow():
-                continue
-            if rc not in (_native.OPOSE_OK, _native.OPOSE_E_CAPACITY, _native.OPOSE_E_ASSEMBLY):
-                self.handle.check(rc)
-            return [self._decode(r) for r in rec]
+        frames, ptr, N, H, W, rs, fs, _ = _native.frames_view(np.asarray(frames))
+        return self._records(N, lambda rec: lib.opose_body_infer(self.handle.h, ptr, N, H, W, rs, fs, self.params,
+                                                                 rec, 0))
 
     def post(self, maps, pad, H, W):
         """Post-network path only (src/body.py:52-212) on one scale.
@@ -85,23 +65,17 @@ class Body(object):
         maps = np.ascontiguousarray(maps, dtype=np.float32)
         N, c, hl, wl = maps.shape
         assert c == 57
-        while True:
-            rec = np.empty((N, self.handle.record_bytes()), np.uint8)
-            rc = _native.lib.opose_body_post(self.handle.h, maps.ctypes.data, N, hl, wl, int(pad[2]), int(pad[3]),
-                                             int(H), int(W), self.params, rec.ctypes.data, 0)
-            if rc == _native.OPOSE_E_CAPACITY and self._grow():
-                continue
-            if rc not in (_native.OPOSE_OK, _native.OPOSE_E_CAPACITY, _native.OPOSE_E_ASSEMBLY):
-                self.handle.check(rc)
-            return [self._decode(r) for r in rec]
+        return self._records(N, lambda rec: lib.opose_body_post(self.handle.h, maps.ctypes.data, N, hl, wl,
+                                                                int(pad[2]), int(pad[3]), int(H), int(W),
+                                                                self.params, rec, 0))
 
     # ------------------------------------------------------------------ per-scale split
     def scale_geom(self, H, W):
         """[(hl, wl, pad_down, pad_right)] per scale of scale_search for an H x W frame."""
         out = []
         for s in range(self.params.n_scales):
-            g = (ctypes_int4)()
-            self.handle.check(_native.lib.opose_body_scale_geom(int(H), int(W), self.params, s, g))
+            g = (ctypes.c_int * 4)()
+            self.handle.check(lib.opose_body_scale_geom(int(H), int(W), self.params, s, g))
             out.append(tuple(int(v) for v in g))
         return out
 
@@ -110,30 +84,20 @@ class Body(object):
 
         frames: uint8 [N,H,W,3] numpy (-> numpy) or a torch cuda tensor (-> torch cuda tensor,
         written into `out` when given, complete in torch's current-stream order)."""
-        if hasattr(frames, "data_ptr"):
+        frames, ptr, N, H, W, rs, fs, dev = _native.frames_view(_as_batch(frames))
+        hl, wl, _, _ = self.scale_geom(H, W)[s]
+        if dev:
             import torch
-            if frames.dim() == 3:
-                frames = frames[None]
-            N, H, W, _ = frames.shape
-            if frames.stride(2) != 3 or frames.stride(3) != 1 or (N > 1 and frames.stride(0) < frames.stride(1) * H):
-                raise ValueError("expected uint8 frames [N, H, W, 3] with packed pixels")
-            hl, wl, _, _ = self.scale_geom(H, W)[s]
             if out is None:
                 out = torch.empty((N, 57, hl, wl), dtype=torch.float32, device=frames.device)
             assert out.is_contiguous() and tuple(out.shape) == (N, 57, hl, wl)
-            self.handle.wait_torch()
-            self.handle.check(_native.lib.opose_body_scale_maps(
-                self.handle.h, frames.data_ptr(), N, H, W, frames.stride(1), max(frames.stride(0), frames.stride(1) * H),
-                self.params, s, out.data_ptr(), _native.IN_DEVICE | _native.OUT_DEVICE))
-            self.handle.signal_torch()  # `out` complete in torch's stream order (e.g. an isend)
+            # `out` complete in torch's stream order (e.g. an isend)
+            self.handle.torch_call(lib.opose_body_scale_maps, ptr, N, H, W, rs, fs, self.params, s, out.data_ptr(),
+                                   _native.DEVICE_IO)
             return out
-        frames = np.ascontiguousarray(frames if np.ndim(frames) == 4 else np.asarray(frames)[None])
-        N, H, W, _ = frames.shape
-        hl, wl, _, _ = self.scale_geom(H, W)[s]
         maps = np.empty((N, 57, hl, wl), np.float32)
-        self.handle.check(_native.lib.opose_body_scale_maps(
-            self.handle.h, frames.ctypes.data, N, H, W, frames.strides[1], frames.strides[1] * H, self.params, s,
-            maps.ctypes.data, 0))
+        self.handle.check(lib.opose_body_scale_maps(self.handle.h, ptr, N, H, W, rs, fs, self.params, s,
+                                                    maps.ctypes.data, 0))
         return maps
 
     def band_maps(self, frame, s, r0, r1, exchange=None):
@@ -150,19 +114,9 @@ class Body(object):
         between the layers).  The bands of a frame put together are scale_maps(frame, s) bit for
         bit: every conv sums a pixel in the whole frame's order."""
         import torch
-        dev = hasattr(frame, "data_ptr")
-        if dev:
-            frame = frame[0] if frame.dim() == 4 else frame
-            if frame.stride(1) != 3 or frame.stride(2) != 1:
-                raise ValueError("expected a uint8 frame [H, W, 3] with packed pixels")
-            H, W, _ = frame.shape
-            ptr, rs = frame.data_ptr(), frame.stride(0)
-        else:
-            frame = np.ascontiguousarray(np.asarray(frame)[0] if np.ndim(frame) == 4 else frame)
-            H, W, _ = frame.shape
-            ptr, rs = frame.ctypes.data, frame.strides[0]
+        frame, ptr, _, H, W, rs, _, dev = _native.frames_view(_as_batch(frame)[:1])
         hl, wl, _, _ = self.scale_geom(H, W)[s]
-        cap = int(_native.lib.opose_body_band_halo_bytes(wl))
+        cap = int(lib.opose_body_band_halo_bytes(wl))
         xbuf = getattr(self, "_band_xbuf", None)  # kept across calls (27 exchanges per call)
         if xbuf is None or xbuf.numel() < 4 * cap:
             xbuf = self._band_xbuf = torch.empty(4 * cap, dtype=torch.uint8,
@@ -180,25 +134,21 @@ class Body(object):
                 return 1
 
         cb = _native.HALO_FN() if exchange == "rccl" else _native.HALO_FN(_cb)  # NULL: the library's RCCL
-        flags = 0
         if dev:
             out = torch.empty((1, 57, r1 - r0, wl), dtype=torch.float32, device=frame.device)
-            self.handle.wait_torch()
-            rc = _native.lib.opose_body_band_maps(self.handle.h, ptr, H, W, rs, self.params, s, r0, r1,
-                                                  out.data_ptr(), cb, None, xbuf.data_ptr(), 4 * cap,
-                                                  flags | _native.IN_DEVICE | _native.OUT_DEVICE)
-            if err:
-                raise err[0]
-            self.handle.check(rc)
-            self.handle.signal_torch()
-            return out
-        self.handle.wait_torch()  # xbuf was allocated on torch's stream
-        out = np.empty((1, 57, r1 - r0, wl), np.float32)
-        rc = _native.lib.opose_body_band_maps(self.handle.h, ptr, H, W, rs, self.params, s, r0, r1, out.ctypes.data,
-                                              cb, None, xbuf.data_ptr(), 4 * cap, flags)
+        else:
+            out = np.empty((1, 57, r1 - r0, wl), np.float32)
+        # not Handle.torch_call: a callback's own exception goes before the library's status, only a
+        # device call that succeeded signals, and a numpy call waits only (xbuf was allocated on
+        # torch's stream) and never signals
+        self.handle.wait_torch()
+        rc = lib.opose_body_band_maps(self.handle.h, ptr, H, W, rs, self.params, s, r0, r1, _native._ptr(out), cb,
+                                      None, xbuf.data_ptr(), 4 * cap, _native.DEVICE_IO if dev else 0)
         if err:
             raise err[0]
         self.handle.check(rc)
+        if dev:
+            self.handle.signal_torch()
         return out
 
     def post_scales(self, maps, H, W):
@@ -219,16 +169,9 @@ class Body(object):
         if dev:
             self.handle.wait_torch()  # e.g. maps received by an irecv on torch's stream
         arr = [(ctypes.c_int * ns)(*[g[i] for g in geoms]) for i in range(4)]
-        while True:
-            rec = np.empty((N, self.handle.record_bytes()), np.uint8)
-            rc = _native.lib.opose_body_post_scales(self.handle.h, ptrs, arr[0], arr[1], arr[2], arr[3], ns, N,
-                                                    int(H), int(W), self.params, rec.ctypes.data,
-                                                    _native.IN_DEVICE if dev else 0)
-            if rc == _native.OPOSE_E_CAPACITY and self._grow():
-                continue
-            if rc not in (_native.OPOSE_OK, _native.OPOSE_E_CAPACITY, _native.OPOSE_E_ASSEMBLY):
-                self.handle.check(rc)
-            return [self._decode(r) for r in rec]
+        return self._records(N, lambda rec: lib.opose_body_post_scales(
+            self.handle.h, ptrs, arr[0], arr[1], arr[2], arr[3], ns, N, int(H), int(W), self.params, rec,
+            _native.IN_DEVICE if dev else 0))
 
     # ------------------------------------------------------------------ device API
     def infer_records(self, frames_dev, records_dev=None, pipeline=False, wait=True):
@@ -249,23 +192,15 @@ class Body(object):
         marker on the caller's stream, and a stream that shares a hardware queue with the
         handle's post-processing stream then holds the next network back behind that work."""
         import torch
-        N, H, W, _ = frames_dev.shape
-        if frames_dev.stride(3) != 1 or frames_dev.stride(2) != 3:
-            frames_dev = frames_dev.contiguous()  # pixels must be packed BGR; rows / frames may be strided
-        # a size-1 axis may carry any stride (0 for a numpy newaxis): give it the dense one
-        row_stride = frames_dev.stride(1) if H > 1 else 3 * W
-        frame_stride = frames_dev.stride(0) if N > 1 else row_stride * H
-        rb = self.handle.record_bytes()
+        frames_dev, ptr, N, H, W, row_stride, frame_stride, _ = _native.frames_view(frames_dev)
         if records_dev is None:
-            records_dev = torch.empty((N, rb), dtype=torch.uint8, device=frames_dev.device)
+            records_dev = torch.empty((N, self.handle.record_bytes()), dtype=torch.uint8, device=frames_dev.device)
         if wait or not pipeline:
             self.handle.wait_torch()  # frames / records produced or last used on torch's stream
-        rc = _native.lib.opose_body_infer(self.handle.h, frames_dev.data_ptr(), N, H, W, row_stride,
-                                          frame_stride, self.params, records_dev.data_ptr(),
-                                          _native.IN_DEVICE | _native.OUT_DEVICE
-                                          | (_native.PIPELINE if pipeline else 0)
-                                          | (_native.PIPELINE_DEFER if pipeline == "defer" else 0))
-        self.handle.check(rc)
+        self.handle.check(lib.opose_body_infer(self.handle.h, ptr, N, H, W, row_stride, frame_stride, self.params,
+                                               records_dev.data_ptr(),
+                                               _native.DEVICE_IO | (_native.PIPELINE if pipeline else 0)
+                                               | (_native.PIPELINE_DEFER if pipeline == "defer" else 0)))
         if pipeline:
             # outputs stay in the handle's stream order (torch's stream must not wait for them, or
             # the next call's network could not overlap this call's post-processing): consumers
@@ -292,14 +227,19 @@ class Body(object):
         self.handle.set_capacity(self.peaks_per_part, self.max_people)
         return True
 
+    def _records(self, N, call):
+        """call(rec_ptr) -> rc fills N host records: run it, with the capacity doubled and the call
+        repeated while a frame overflows its record, and decode -> list of (candidate, subset)."""
+        while True:
+            rec = np.empty((N, self.handle.record_bytes()), np.uint8)
+            rc = call(rec.ctypes.data)
+            if rc == _native.OPOSE_E_CAPACITY and self._grow():
+                continue
+            if rc not in (_native.OPOSE_OK, _native.OPOSE_E_CAPACITY, _native.OPOSE_E_ASSEMBLY):
+                self.handle.check(rc)  # the two let through are per-frame statuses: _decode raises them
+            return [self._decode(r) for r in rec]
+
     def _decode(self, rec):
         status, cand, subset = _native.decode_record(rec, self.peaks_per_part, self.max_people)
-        if status == _native.OPOSE_E_ASSEMBLY:
-            # the reference raises here when a third subset row matches (src/body.py:170-173)
-            raise IndexError("list assignment index out of range")
-        if status == _native.OPOSE_E_CAPACITY:
-            raise RuntimeError("libopose: per-frame capacity exceeded (peaks_per_part=%d, max_people=%d)"
-                               % (self.peaks_per_part, self.max_people))
-        if status != 0:
-            raise _native.OposeError(status, "frame failed")
+        _native.raise_record_status(status, self.peaks_per_part, self.max_people)
         return cand, subset

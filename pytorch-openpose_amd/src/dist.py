@@ -164,7 +164,8 @@ def band_exchange(rank_up, rank_dn, group=None, timeout: float | None = None):
     P2P ops ordered on the library's stream; gloo: through host memory, synchronously, each
     send / recv waited for at most `timeout` seconds (None: the process group's own timeout), so
     the neighbour of a rank that failed mid-band raises instead of blocking in its next exchange
-    (the library reports the callback's error as OPOSE_E_CALLBACK)."""
+    (the library answers a failed callback with OPOSE_E_WEIGHTS, "row band: halo exchange failed";
+    Body.band_maps raises the callback's own exception instead)."""
     wait_kw = {} if timeout is None else {"timeout": datetime.timedelta(seconds=timeout)}
 
     def ex(xbuf, cap, n, stream):

@@ -17,21 +17,20 @@ import ctypes as C
 
 import numpy as np
 
-from . import _native, util
-from .model import handpose_model
+from . import _native
+from .model import handpose_model, load_model
 
 
-def _load_state(model_path):
-    if isinstance(model_path, dict):
-        return model_path
-    import torch
-    return torch.load(model_path, map_location="cpu", weights_only=True)
+def hand_outputs(N):
+    """The arrays every hand entry point fills: peaks float64 [N, 21, 3], found int32 [N, 21]."""
+    return np.empty((N, 21, 3), np.float64), np.empty((N, 21), np.int32)
 
 
 def _as_reference_array(peaks: np.ndarray, found: np.ndarray) -> np.ndarray:
-    """np.array(all_peaks) semantics: int64 when every row is the [0, 0, 0] placeholder."""
+    """np.array(all_peaks) semantics: absent parts are [0, 0, 0] rows, and the array is int64
+    when every row is that placeholder (one hand [21, 3], or a whole Batch_hand batch)."""
     if not found.any():
-        return np.zeros((21, 3), dtype=np.int64)
+        return np.zeros(peaks.shape, dtype=np.int64)
     out = peaks.copy()
     out[~found.astype(bool)] = 0.0
     return out
@@ -40,9 +39,7 @@ def _as_reference_array(peaks: np.ndarray, found: np.ndarray) -> np.ndarray:
 class Hand(object):
     def __init__(self, model_path, device: int = 0, scale_search=(0.5, 1.0, 1.5, 2.0), boxsize=368, stride=8,
                  padValue=128, thre=0.03):
-        self.model = handpose_model(device)
-        self.model.load_state_dict(util.transfer(self.model, _load_state(model_path)))
-        self.model.eval()
+        self.model = load_model(handpose_model, model_path, device)
         self.handle = self.model.handle
         self.params = _native.default_params(_native.NET_HAND, scale_search=scale_search, boxsize=float(boxsize),
                                              stride=int(stride), pad_value=int(padValue), thre_hand=float(thre))
@@ -52,18 +49,10 @@ class Hand(object):
 
     def batch(self, crops):
         """crops: uint8 [N, h, w, 3] of equal size -> list of [21, 3] arrays."""
-        crops = np.asarray(crops)
-        if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
-            raise ValueError("expected uint8 crops [N, h, w, 3]")
-        if not (crops.strides[3] == 1 and crops.strides[2] == 3 and crops.strides[1] >= 3 * crops.shape[2]
-                and (crops.shape[0] == 1 or crops.strides[0] >= crops.strides[1] * crops.shape[1])):
-            crops = np.ascontiguousarray(crops)
-        N, H, W, _ = crops.shape
-        fs = crops.strides[0] if N > 1 else crops.strides[1] * H
-        peaks = np.empty((N, 21, 3), np.float64)
-        found = np.empty((N, 21), np.int32)
-        self.handle.check(_native.lib.opose_hand_infer(self.handle.h, crops.ctypes.data, N, H, W, crops.strides[1], fs,
-                                                       self.params, peaks.ctypes.data, found.ctypes.data, 0))
+        crops, ptr, N, H, W, rs, fs, _ = _native.frames_view(np.asarray(crops), "crops")
+        peaks, found = hand_outputs(N)
+        self.handle.check(_native.lib.opose_hand_infer(self.handle.h, ptr, N, H, W, rs, fs, self.params,
+                                                       peaks.ctypes.data, found.ctypes.data, 0))
         return [_as_reference_array(peaks[i], found[i]) for i in range(N)]
 
     def batch_crops(self, crops):
@@ -83,8 +72,7 @@ class Hand(object):
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
         sizes = np.array([a.shape[0] for a in arrs], np.int32)
         strides = np.array([a.strides[0] for a in arrs], np.int64)
-        peaks = np.empty((n, 21, 3), np.float64)
-        found = np.empty((n, 21), np.int32)
+        peaks, found = hand_outputs(n)
         self.handle.check(_native.lib.opose_hand_infer_crops(self.handle.h, ptrs, sizes.ctypes.data, strides.ctypes.data,
                                                              n, self.params, peaks.ctypes.data, found.ctypes.data, 0))
         return [_as_reference_array(peaks[i], found[i]) for i in range(n)]
@@ -102,8 +90,7 @@ class Hand(object):
         wl = np.array([a.shape[3] for a in arrs], np.int32)
         pd = np.array([p[2] for p in pads], np.int32)
         pr = np.array([p[3] for p in pads], np.int32)
-        peaks = np.empty((N, 21, 3), np.float64)
-        found = np.empty((N, 21), np.int32)
+        peaks, found = hand_outputs(N)
         self.handle.check(_native.lib.opose_hand_post(self.handle.h, ptrs, hl.ctypes.data, wl.ctypes.data,
                                                       pd.ctypes.data, pr.ctypes.data, ns, N, int(H), int(W),
                                                       self.params, peaks.ctypes.data, found.ctypes.data, 0))

@@ -20,7 +20,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import _native
+from . import _native, util
 
 _VGG_BODY = [("conv1_1", 3, 64, 3, 1), ("conv1_2", 64, 64, 3, 1), ("conv2_1", 64, 128, 3, 1),
              ("conv2_2", 128, 128, 3, 1), ("conv3_1", 128, 256, 3, 1), ("conv3_2", 256, 256, 3, 1),
@@ -106,6 +106,40 @@ class _DeviceNet:
     def __call__(self, x):
         return self.forward(x)
 
+    def _forward(self, x, fn, channels):
+        """fn (opose_body_forward / opose_hand_forward) on x: one [N, c, H/8, W/8] float32 output
+        per entry of channels, torch tensors on x's device for a cuda tensor, else numpy arrays."""
+        N, c, H, W = x.shape
+        if c != 3 or H % 8 or W % 8:
+            raise ValueError("input must be [N,3,H,W] with H, W multiples of 8")
+        shapes = [(N, ch, H // 8, W // 8) for ch in channels]
+        if hasattr(x, "is_cuda") and x.is_cuda:
+            import torch
+            xt = x.contiguous().float()
+            outs = [torch.empty(s, device=x.device) for s in shapes]
+            # xt may still be in flight on torch's stream; outputs ready (and xt free to reuse) in its order
+            self.handle.torch_call(fn, xt.data_ptr(), N, H, W, *[o.data_ptr() for o in outs], _native.DEVICE_IO)
+            return outs
+        xn = np.ascontiguousarray(x.numpy() if hasattr(x, "numpy") else x, dtype=np.float32)
+        outs = [np.empty(s, np.float32) for s in shapes]
+        self.handle.check(fn(self.handle.h, xn.ctypes.data, N, H, W, *[o.ctypes.data for o in outs], 0))
+        return outs
+
+
+def _load_state(model_path):
+    if isinstance(model_path, dict):
+        return model_path
+    import torch
+    return torch.load(model_path, map_location="cpu", weights_only=True)
+
+
+def load_model(cls, model_path, device: int = 0):
+    """cls (bodypose_model / handpose_model) on `device` with the weights of model_path (a .pth
+    file or a state dict), loaded the way the reference does (src/body.py:17-22)."""
+    model = cls(device)
+    model.load_state_dict(util.transfer(model, _load_state(model_path)))
+    return model.eval()
+
 
 class bodypose_model(_DeviceNet):
     """forward(x[N,3,H,W] fp32) -> (paf[N,38,H/8,W/8], heat[N,19,H/8,W/8]) (src/model.py:106-133)."""
@@ -113,25 +147,7 @@ class bodypose_model(_DeviceNet):
     NET = "body"
 
     def forward(self, x):
-        N, c, H, W = x.shape
-        if c != 3 or H % 8 or W % 8:
-            raise ValueError("input must be [N,3,H,W] with H, W multiples of 8")
-        if hasattr(x, "is_cuda") and x.is_cuda:
-            import torch
-            xt = x.contiguous().float()
-            paf = torch.empty((N, 38, H // 8, W // 8), device=x.device)
-            heat = torch.empty((N, 19, H // 8, W // 8), device=x.device)
-            self.handle.wait_torch()  # xt may still be in flight on torch's stream
-            self.handle.check(_native.lib.opose_body_forward(self.handle.h, xt.data_ptr(), N, H, W, paf.data_ptr(),
-                                                             heat.data_ptr(), _native.IN_DEVICE | _native.OUT_DEVICE))
-            self.handle.signal_torch()  # outputs ready (and xt free to reuse) in torch's stream order
-            return paf, heat
-        xn = np.ascontiguousarray(x.numpy() if hasattr(x, "numpy") else x, dtype=np.float32)
-        paf = np.empty((N, 38, H // 8, W // 8), np.float32)
-        heat = np.empty((N, 19, H // 8, W // 8), np.float32)
-        self.handle.check(_native.lib.opose_body_forward(self.handle.h, xn.ctypes.data, N, H, W, paf.ctypes.data,
-                                                         heat.ctypes.data, 0))
-        return paf, heat
+        return tuple(self._forward(x, _native.lib.opose_body_forward, (38, 19)))
 
 
 class handpose_model(_DeviceNet):
@@ -140,22 +156,7 @@ class handpose_model(_DeviceNet):
     NET = "hand"
 
     def forward(self, x):
-        N, c, H, W = x.shape
-        if c != 3 or H % 8 or W % 8:
-            raise ValueError("input must be [N,3,H,W] with H, W multiples of 8")
-        if hasattr(x, "is_cuda") and x.is_cuda:
-            import torch
-            xt = x.contiguous().float()
-            heat = torch.empty((N, 22, H // 8, W // 8), device=x.device)
-            self.handle.wait_torch()
-            self.handle.check(_native.lib.opose_hand_forward(self.handle.h, xt.data_ptr(), N, H, W, heat.data_ptr(),
-                                                             _native.IN_DEVICE | _native.OUT_DEVICE))
-            self.handle.signal_torch()
-            return heat
-        xn = np.ascontiguousarray(x.numpy() if hasattr(x, "numpy") else x, dtype=np.float32)
-        heat = np.empty((N, 22, H // 8, W // 8), np.float32)
-        self.handle.check(_native.lib.opose_hand_forward(self.handle.h, xn.ctypes.data, N, H, W, heat.ctypes.data, 0))
-        return heat
+        return self._forward(x, _native.lib.opose_hand_forward, (22,))[0]
 
     def forward_pyramid(self, xs):
         """The networks of a scale pyramid in one lockstep pass (what Hand() runs for its

@@ -153,11 +153,8 @@ class _DeviceIngest(object):
             status, cand, subset = _native.decode_record(r, *self.layout[i])
             if status == _native.OPOSE_E_CAPACITY:
                 out.extend(self.body.batch(np.ascontiguousarray(f)[None]))
-            elif status == _native.OPOSE_E_ASSEMBLY:
-                raise IndexError("list assignment index out of range")  # src/body.py:170-173
-            elif status != 0:
-                raise _native.OposeError(status, "frame failed")
             else:
+                _native.raise_record_status(status, *self.layout[i])
                 out.append((cand, subset))
         return out
 
