@@ -20,6 +20,8 @@
  *                                  69-104                    opose_batch_hand_crops (parity entry point)
  *   Batch_hand_extraction's loop   srcmx/Batch_motion_       opose_batch_hand_extract
  *                                  Estimation.py:19-65
+ *   Batch_body_extraction's loop   srcmx/Batch_motion_       opose_batch_body_extract;
+ *                                  Estimation.py:83-108      opose_body_records_pose (parity entry point)
  *   one scale of Body.__call__     src/body.py:36-50         opose_body_scale_maps; its output rows
  *                                                            opose_body_band_maps (C5 split)
  *
@@ -290,6 +292,31 @@ int opose_batch_hand_crops(opose_t* h, const uint8_t* bgr, int N, int H, int W, 
 int opose_batch_hand_extract(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
                              int64_t frame_stride, const double* motion, int boxsize, const opose_params* p,
                              double* handmat, int32_t* status, int flags);
+
+/* ---- fast-mode body extraction (srcmx/Batch_motion_Estimation.py:68-113 Batch_body_extraction) -- */
+/* The loop body of Batch_body_extraction (:88-107) on N Body records (made by opose_body_infer,
+ * opose_batch_body_infer or a *_post entry point at the handle's current capacity; 8-byte
+ * aligned): per frame the person with the largest left-shoulder x -- candidate[int(subset[p][5])][0],
+ * an absent shoulder's -1 reading the last candidate row as Python's negative index does, the
+ * first person among equal maxima as np.argmax -- and that person's keypoints as a PoseMat row
+ * pose [N][18][3] (x, y, score; a missing keypoint, and every row of a frame without people, is
+ * 0, 0, 0).  The values are copied: bit-exact float64.  status [N]: OPOSE_OK; the record's own
+ * status when that is not OPOSE_OK (zero row; the rest of the record is not read); OPOSE_E_ARG for
+ * a record whose subset names a candidate row it does not hold (zero row; no address outside the
+ * record is read).  Records and outputs are host memory, or device memory with OPOSE_IN_DEVICE /
+ * OPOSE_OUT_DEVICE; with OPOSE_OUT_DEVICE the call is asynchronous on the handle's stream and
+ * returns OPOSE_OK (the per-frame status is the caller's to read), else it returns the worst
+ * per-frame status.  Parity entry point. */
+int opose_body_records_pose(opose_t* h, const void* records, int N, double* pose, int32_t* status, int flags);
+
+/* N frames -> PoseMat rows: opose_batch_body_infer into a record buffer the library owns, then
+ * opose_body_records_pose on it, on the handle's stream with no host round trip in between; the
+ * records never leave the device.  Arguments as opose_batch_body_infer, pose / status / the return
+ * value as opose_body_records_pose (a frame that overflows the record capacity: OPOSE_E_CAPACITY
+ * and a zero row). */
+int opose_batch_body_extract(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                             int64_t frame_stride, const opose_params* p, double* pose, int32_t* status,
+                             int flags);
 
 /* Hand on N crops uint8 [H][W][3] (util.handDetect gives squares): peaks [N][21][3]
  * (x, y, score), found [N][21] (0 = part missing, the reference's [0,0,0] row). */

@@ -387,6 +387,9 @@ struct opose_ctx {
     // fast-mode hand extraction (opose_batch_hand_boxes / _crops / _extract): staged poses, the
     // boxes and per-slot status, staged results
     opose::DevBuf hx_motion, hx_boxes, hx_status, hx_crops, hx_handmat;
+    // fast-mode body extraction (opose_body_records_pose / opose_batch_body_extract): staged poses
+    // and per-frame status (the records are in `records`)
+    opose::DevBuf px_pose, px_status;
     // opose_batch_hand_extract cuts its 2N crops into chunks the conv kernels can address (as
     // opose_hand_infer_crops does); OPOSE_EXTRACT_CHUNK=n at handle creation: n crops per chunk
     // instead (tests/test_gpu_hand_extract.py runs a small batch in two chunks)

@@ -540,6 +540,33 @@ int opose_body_post_scales(opose_t* h, const float* const* maps, const int* hl, 
     });
 }
 
+// The fast mode's launch sequence from the caller's frames to the records at rec_of() on the device
+// (opose_batch_body_infer, opose_batch_body_extract): rec_of() names the destination once the
+// frames are staged.  Returns it.
+template <class F>
+static uint8_t* run_batch_body(opose_ctx* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                               int64_t frame_stride, const opose_params& p, int flags, F&& rec_of) {
+    // Batch_body.calculate_size_pad (srcmx/Batch_model.py:302-307): int() truncation
+    const double scale = p.boxsize * p.scales[0] / H;
+    const int nh = (int)(H * scale), nw = (int)(W * scale);
+    if (nh <= 0 || nw <= 0) throw std::invalid_argument("scale produces an empty image");
+    const int Hp = round_up(nh, p.stride), Wp = round_up(nw, p.stride);
+    const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, flags);
+    uint8_t* rec = rec_of();
+    const std::string key = call_key("batch_body", N, H, W, row_stride, frame_stride, p, fd, rec, h->ppp, h->maxp);
+    run_graphed(h, key, [&] {
+        float* x = h->w().x.ensure<float>((size_t)N * 3 * Hp * Wp, h->stream);
+        ProfEntry pe;
+        h->prof_begin(pe, "preprocess", 0, (double)N * (3.0 * H * W + 12.0 * Hp * Wp));
+        const float sc = (float)(1.0 / scale);  // torch: float(1 / scale_factor)
+        launch_preprocess_torch(fd, frame_stride, row_stride, N, H, W, nh, nw, sc, sc, Hp, Wp, x, h->stream);
+        h->prof_end(pe);
+        float* S = body_net(h, x, N, Hp, Wp);
+        batch_post_common(h, N, H, W, S, 185, Hp / 8, Wp / 8, nh, nw, p, rec);
+    });
+    return rec;
+}
+
 int opose_batch_body_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
                            int64_t frame_stride, const opose_params* pp, void* records, int flags) {
     if (!h || !bgr || !records || N <= 0 || H <= 0 || W <= 0) return OPOSE_E_ARG;
@@ -547,24 +574,8 @@ int opose_batch_body_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, 
     OPOSE_TRY(h, {
         enter_main(h);
         const opose_params p = fill_params(pp, OPOSE_NET_BODY);
-        // Batch_body.calculate_size_pad (srcmx/Batch_model.py:302-307): int() truncation
-        const double scale = p.boxsize * p.scales[0] / H;
-        const int nh = (int)(H * scale), nw = (int)(W * scale);
-        if (nh <= 0 || nw <= 0) throw std::invalid_argument("scale produces an empty image");
-        const int Hp = round_up(nh, p.stride), Wp = round_up(nw, p.stride);
-        const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, flags);
-        uint8_t* rec = records_dest(h, N, records, flags);
-        const std::string key = call_key("batch_body", N, H, W, row_stride, frame_stride, p, fd, rec, h->ppp, h->maxp);
-        run_graphed(h, key, [&] {
-            float* x = h->w().x.ensure<float>((size_t)N * 3 * Hp * Wp, h->stream);
-            ProfEntry pe;
-            h->prof_begin(pe, "preprocess", 0, (double)N * (3.0 * H * W + 12.0 * Hp * Wp));
-            const float sc = (float)(1.0 / scale);  // torch: float(1 / scale_factor)
-            launch_preprocess_torch(fd, frame_stride, row_stride, N, H, W, nh, nw, sc, sc, Hp, Wp, x, h->stream);
-            h->prof_end(pe);
-            float* S = body_net(h, x, N, Hp, Wp);
-            batch_post_common(h, N, H, W, S, 185, Hp / 8, Wp / 8, nh, nw, p, rec);
-        });
+        uint8_t* rec = run_batch_body(h, bgr, N, H, W, row_stride, frame_stride, p, flags,
+                                      [&] { return records_dest(h, N, records, flags); });
         return finish_records(h, N, records, rec, flags);
     });
 }
@@ -790,6 +801,64 @@ int opose_batch_hand_extract(opose_t* h, const uint8_t* bgr, int N, int H, int W
         h->prof_drain();
         if (worst != OPOSE_OK) h->err = "a present hand box is empty or leaves the frame";
         return worst;
+    });
+}
+
+// ---- fast-mode body extraction (srcmx/Batch_motion_Estimation.py:68-113) -----------------------
+// pose_select on N device records -> pose / status: the caller's device pointers (out_device;
+// asynchronous, OPOSE_OK) or the handle's buffers copied to the host, then the worst status
+static int run_pose_select(opose_ctx* h, const uint8_t* rec_dev, int N, double* pose, int32_t* status,
+                           bool out_device) {
+    double* pd = out_device ? pose : h->px_pose.ensure<double>((size_t)N * 54, h->stream);
+    int32_t* sd = out_device ? status : h->px_status.ensure<int32_t>((size_t)N, h->stream);
+    ProfEntry pe;
+    h->prof_begin(pe, "pose_select", 0, (double)N * (54 * 8 + 4));
+    launch_pose_select(rec_dev, N, make_record_layout(h->ppp, h->maxp), pd, sd, h->stream);
+    h->prof_end(pe);
+    if (out_device) {
+        h->prof_drain();
+        return OPOSE_OK;
+    }
+    OPOSE_HIP_CHECK(hipMemcpyAsync(pose, pd, sizeof(double) * N * 54, hipMemcpyDeviceToHost, h->stream));
+    const int worst = worst_slot_status(h, sd, N, status);
+    h->prof_drain();
+    if (worst != OPOSE_OK) h->err = "a frame's record carries a status, or indexes past its candidates";
+    return worst;
+}
+
+int opose_body_records_pose(opose_t* h, const void* records, int N, double* pose, int32_t* status, int flags) {
+    if (!h || !records || !pose || !status || N <= 0) return OPOSE_E_ARG;
+    if (reinterpret_cast<uintptr_t>(records) % 8) return OPOSE_E_ARG;  // float64 rows at offset 16
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const uint8_t* rd = static_cast<const uint8_t*>(records);
+        if (!(flags & OPOSE_IN_DEVICE)) {
+            const size_t bytes = make_record_layout(h->ppp, h->maxp).bytes * N;
+            uint8_t* buf = h->records.ensure<uint8_t>(bytes, h->stream);
+            OPOSE_HIP_CHECK(hipMemcpyAsync(buf, records, bytes, hipMemcpyHostToDevice, h->stream));
+            rd = buf;
+        }
+        return run_pose_select(h, rd, N, pose, status, flags & OPOSE_OUT_DEVICE);
+    });
+}
+
+int opose_batch_body_extract(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                             int64_t frame_stride, const opose_params* pp, double* pose, int32_t* status, int flags) {
+    if (!h || !bgr || !pose || !status || N <= 0 || H <= 0 || W <= 0) return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const opose_params p = fill_params(pp, OPOSE_NET_BODY);
+        // the records stay in the handle's buffer, sized (with the staged results) before anything
+        // is enqueued.  The launch sequence is opose_batch_body_infer's into that buffer, under
+        // that call's key; pose_select follows it eagerly on the same stream.
+        uint8_t* rec = h->records.ensure<uint8_t>(make_record_layout(h->ppp, h->maxp).bytes * N, h->stream);
+        if (!(flags & OPOSE_OUT_DEVICE)) {
+            h->px_pose.ensure<double>((size_t)N * 54, h->stream);
+            h->px_status.ensure<int32_t>((size_t)N, h->stream);
+        }
+        run_batch_body(h, bgr, N, H, W, row_stride, frame_stride, p, flags, [&] { return rec; });
+        return run_pose_select(h, rec, N, pose, status, flags & OPOSE_OUT_DEVICE);
     });
 }
 

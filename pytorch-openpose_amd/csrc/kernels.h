@@ -131,6 +131,10 @@ void launch_hand_crops(const uint8_t* src, int64_t frame_stride, int64_t row_str
 void launch_hand_backmap(const double* peaks, const int32_t* found, const int32_t* boxes, int N, int bs,
                          double* handmat, hipStream_t st);
 
+// posemat.hip: the fast mode's person choice, N records of layout L -> pose [N][18][3], status [N]
+void launch_pose_select(const uint8_t* records, int N, const RecordLayout& L, double* pose, int32_t* status,
+                        hipStream_t st);
+
 // post.hip
 void launch_gauss_nms(const void* avg, bool f32, int NP, int H, int W, double thre, int cap, int* cnt, int* list,
                       double* list_score, hipStream_t st);

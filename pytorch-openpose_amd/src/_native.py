@@ -74,6 +74,8 @@ SIGNATURES = {
     "opose_batch_hand_boxes": (_I, [_P, _P, _I, _I, _I, _P, _I]),
     "opose_batch_hand_crops": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _I, _P, _I]),
     "opose_batch_hand_extract": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _I, C.POINTER(Params), _P, _P, _I]),
+    "opose_body_records_pose": (_I, [_P, _P, _I, _P, _P, _I]),
+    "opose_batch_body_extract": (_I, [_P, _P, _I, _I, _I, _L, _L, C.POINTER(Params), _P, _P, _I]),
     "opose_profile_enable": (_I, [_P, _I]),
     "opose_profile_reset": (_I, [_P]),
     "opose_profile_read": (_I, [_P, C.c_char_p, _S]),

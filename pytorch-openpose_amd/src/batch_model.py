@@ -48,6 +48,16 @@ def _as_uint8_frames(batch_images) -> np.ndarray:
     raise ValueError("expected a [B,3,h,w] float batch in [0,1] or uint8 frames [B,h,w,3]")
 
 
+def _frames_view(frames, recpoint):
+    """_native.frames_view of frames [N, H, W, 3] uint8 (numpy, or a torch CUDA tensor) cut to
+    recpoint [(x0, y0), (x1, y1)]: the region of interest is a pointer offset, not a copy."""
+    if not hasattr(frames, "data_ptr"):
+        frames = np.asarray(frames)
+    if recpoint is not None and frames.ndim == 4:
+        frames = frames[:, recpoint[0][1]:recpoint[1][1], recpoint[0][0]:recpoint[1][0], :]
+    return _native.frames_view(frames)
+
+
 class Batch_body(Body):
     def __init__(self, model_path, device: int = 0, scale_search=0.5, boxsize=368, stride=8, thre1=0.1, thre2=0.05,
                  peaks_per_part=128, max_people=96):
@@ -84,6 +94,46 @@ class Batch_body(Body):
                                _native.DEVICE_IO)
         return records_dev
 
+    # ---- body extraction: the loop body of Batch_body_extraction
+    # (srcmx/Batch_motion_Estimation.py:83-108) on the device
+    def extract_device(self, frames_dev, recpoint=None):
+        """Torch CUDA uint8 frames [N, H, W, 3] cut to recpoint [(x0, y0), (x1, y1)] (a pointer
+        offset) -> (PoseMat rows float64 [N, 18, 3], status int32 [N]) as CUDA tensors, in one
+        launch sequence (opose_batch_body_extract): the records stay in the library, the person
+        with the largest left-shoulder x is chosen there (Body.poses).  Asynchronous: ordered after
+        torch's current stream and complete in its order; no host round trip and no retry -- a
+        frame that overflows the record capacity has status OPOSE_E_CAPACITY and a zero row."""
+        import torch
+        v, ptr, N, H, W, rs, fs, dev = _frames_view(frames_dev, recpoint)
+        if not dev:
+            raise ValueError("extract_device needs frames on the device")
+        pose = torch.empty((N, 18, 3), dtype=torch.float64, device=v.device)
+        status = torch.empty((N,), dtype=torch.int32, device=v.device)
+        self.handle.torch_call(lib.opose_batch_body_extract, ptr, N, H, W, rs, fs, self.params, pose.data_ptr(),
+                               status.data_ptr(), _native.DEVICE_IO)
+        return pose, status
+
+    def extract(self, frames, recpoint=None):
+        """N frames (numpy [N, H, W, 3] uint8, or a torch CUDA uint8 tensor) cut to recpoint ->
+        the rows of MotionMat Batch_body_extraction stores for them, float64 [N, 18, 3]:
+        src.pipeline.selected_pose of every frame's (candidate, subset), without the records
+        leaving the device.  Like Body(), a frame that overflows the record capacity doubles it and
+        repeats the call; other per-frame statuses raise what Body() raises."""
+        v, ptr, N, H, W, rs, fs, dev = _frames_view(frames, recpoint)
+        while True:
+            if dev:
+                pose, status = (t.cpu().numpy() for t in self.extract_device(v))
+            else:
+                pose, status = np.zeros((N, 18, 3), np.float64), np.zeros((N,), np.int32)
+                rc = lib.opose_batch_body_extract(self.handle.h, ptr, N, H, W, rs, fs, self.params, pose.ctypes.data,
+                                                  status.ctypes.data, 0)
+                self._check_worst(rc, status)
+            if (status == _native.OPOSE_E_CAPACITY).any() and self._grow():
+                continue
+            for s in status:
+                _native.raise_record_status(int(s), self.peaks_per_part, self.max_people)
+            return pose
+
 
 class Batch_hand(object):
     """srcmx/Batch_model.py:310-354: crops already resized to boxsize (the data loader's
@@ -117,18 +167,12 @@ class Batch_hand(object):
 
     # ---- hand extraction: HandImageDataset (srcmx/Batch_model.py:55-104) and the loop body of
     # Batch_hand_extraction (srcmx/Batch_motion_Estimation.py:29-60) on the device
-    @staticmethod
-    def _frames_view(frames, recpoint):
-        """_native.frames_view of frames [N, H, W, 3] uint8 (numpy, or a torch CUDA tensor) cut to
-        recpoint [(x0, y0), (x1, y1)]: the region of interest is a pointer offset, not a copy."""
-        if not hasattr(frames, "data_ptr"):
-            frames = np.asarray(frames)
-        if recpoint is not None and frames.ndim == 4:
-            frames = frames[:, recpoint[0][1]:recpoint[1][1], recpoint[0][0]:recpoint[1][0], :]
-        return _native.frames_view(frames)
+    _frames_view = staticmethod(_frames_view)
 
     @staticmethod
     def _motion(motion, N):
+        if hasattr(motion, "cpu"):
+            motion = motion.cpu().numpy()
         motion = np.ascontiguousarray(motion, dtype=np.float64)
         if motion.shape != (N, 18, 3):
             raise ValueError("expected one body pose [18, 3] per frame: motion [%d, 18, 3]" % N)
@@ -170,19 +214,37 @@ class Batch_hand(object):
         self.handle.check(rc)
         return out
 
+    def extract_device(self, frames_dev, motion_dev, boxsize=368, recpoint=None):
+        """extract_status() with everything on the device: torch CUDA uint8 frames [N, H, W, 3] and
+        torch CUDA float64 poses [N, 18, 3] (e.g. Batch_body.extract_device's) -> (HandMat rows
+        float64 [N, 42, 3], status int32 [N, 2]) as CUDA tensors.  Asynchronous: ordered after
+        torch's current stream and complete in its order, no host round trip."""
+        import torch
+        v, ptr, N, H, W, rs, fs, dev = self._frames_view(frames_dev, recpoint)
+        if not dev:
+            raise ValueError("extract_device needs frames on the device")
+        if not (hasattr(motion_dev, "is_cuda") and motion_dev.is_cuda and motion_dev.dtype == torch.float64
+                and tuple(motion_dev.shape) == (N, 18, 3)):
+            raise ValueError("expected one body pose [18, 3] per frame: a CUDA float64 motion [%d, 18, 3]" % N)
+        m = motion_dev.contiguous()
+        handmat = torch.empty((N, 42, 3), dtype=torch.float64, device=v.device)
+        status = torch.empty((N, 2), dtype=torch.int32, device=v.device)
+        self.handle.torch_call(lib.opose_batch_hand_extract, ptr, N, H, W, rs, fs, m.data_ptr(), int(boxsize),
+                               self.params, handmat.data_ptr(), status.data_ptr(), _native.DEVICE_IO)
+        return handmat, status
+
     def extract_status(self, frames, motion, boxsize=368, recpoint=None):
         """extract() without its check: (HandMat rows float64 [N, 42, 3], status int32 [N, 2]), a
-        slot's status OPOSE_E_SHAPE where a present hand's box is empty."""
+        slot's status OPOSE_E_SHAPE where a present hand's box is empty.  With frames on the device,
+        motion may be a torch CUDA float64 tensor too: it is then used where it is."""
         v, ptr, N, H, W, rs, fs, dev = self._frames_view(frames, recpoint)
-        motion = self._motion(motion, N)
         if dev:
             import torch
-            m = torch.from_numpy(motion).to(v.device)
-            handmat = torch.empty((N, 42, 3), dtype=torch.float64, device=v.device)
-            status = torch.empty((N, 2), dtype=torch.int32, device=v.device)
-            self.handle.torch_call(lib.opose_batch_hand_extract, ptr, N, H, W, rs, fs, m.data_ptr(), int(boxsize),
-                                   self.params, handmat.data_ptr(), status.data_ptr(), _native.DEVICE_IO)
+            if not (hasattr(motion, "is_cuda") and motion.is_cuda):
+                motion = torch.from_numpy(self._motion(motion, N)).to(v.device)
+            handmat, status = self.extract_device(v, motion, boxsize)
             return handmat.cpu().numpy(), status.cpu().numpy()
+        motion = self._motion(motion, N)
         handmat = np.empty((N, 42, 3), np.float64)
         status = np.empty((N, 2), np.int32)
         rc = lib.opose_batch_hand_extract(self.handle.h, ptr, N, H, W, rs, fs, motion.ctypes.data, int(boxsize),
@@ -198,8 +260,13 @@ class Batch_hand(object):
         launch sequence on the device: boxes, crops, the hand network, Batch_hand's
         post-processing, the back-mapping of Batch_hand_extraction's loop."""
         handmat, status = self.extract_status(frames, motion, boxsize, recpoint)
+        self.raise_status(status)
+        return handmat
+
+    @classmethod
+    def raise_status(cls, status):
+        """The per-slot status [N, 2] of an extraction as extract() raises it (nothing when all 0)."""
         if (status == _native.OPOSE_E_SHAPE).any():
-            self._raise_empty(status == _native.OPOSE_E_SHAPE)
+            cls._raise_empty(status == _native.OPOSE_E_SHAPE)
         if (status != 0).any():
             raise _native.OposeError(int(status.min()), "hand extraction failed")
-        return handmat

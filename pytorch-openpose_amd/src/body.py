@@ -218,7 +218,45 @@ class Body(object):
             records = records.cpu().numpy()
         return [self._decode(r) for r in np.asarray(records)]
 
+    def poses(self, records):
+        """uint8 [N, record_bytes] records of the handle's current capacity -> (pose float64
+        [N, 18, 3], status int32 [N]): per frame the keypoints of the person with the largest
+        left-shoulder x, the row `Batch_body_extraction` keeps (srcmx/Batch_motion_Estimation.py:
+        88-107; src.pipeline.selected_pose on the decoded record), chosen and gathered on the
+        device (opose_body_records_pose).  status: 0, the record's own status (zero row), or
+        OPOSE_E_ARG for a record that indexes past its candidates (zero row).  numpy records give
+        numpy results; a torch CUDA tensor gives CUDA tensors with no synchronisation, complete in
+        torch's current-stream order."""
+        rb = self.handle.record_bytes()
+        if hasattr(records, "data_ptr") and records.is_cuda:
+            import torch
+            if records.dtype != torch.uint8 or records.dim() != 2 or records.shape[1] != rb or len(records) < 1:
+                raise ValueError("expected uint8 records [N, %d]" % rb)
+            records = records.contiguous()
+            N = len(records)
+            pose = torch.empty((N, 18, 3), dtype=torch.float64, device=records.device)
+            status = torch.empty((N,), dtype=torch.int32, device=records.device)
+            self.handle.torch_call(lib.opose_body_records_pose, records.data_ptr(), N, pose.data_ptr(),
+                                   status.data_ptr(), _native.DEVICE_IO)
+            return pose, status
+        if hasattr(records, "cpu"):
+            records = records.cpu().numpy()
+        records = np.ascontiguousarray(records)
+        if records.dtype != np.uint8 or records.ndim != 2 or records.shape[1] != rb or len(records) < 1:
+            raise ValueError("expected uint8 records [N, %d]" % rb)
+        N = len(records)
+        pose, status = np.zeros((N, 18, 3), np.float64), np.zeros((N,), np.int32)
+        rc = lib.opose_body_records_pose(self.handle.h, records.ctypes.data, N, pose.ctypes.data, status.ctypes.data, 0)
+        self._check_worst(rc, status)
+        return pose, status
+
     # ------------------------------------------------------------------ helpers
+    def _check_worst(self, rc, status):
+        """rc of a call that returns its worst per-frame status, `status` zeroed before the call: a
+        code no frame carries is the call's own failure."""
+        if rc != _native.OPOSE_OK and rc != int(status.min()):
+            self.handle.check(rc)
+
     def _grow(self) -> bool:
         if self.peaks_per_part >= 1024 and self.max_people >= 256:
             return False

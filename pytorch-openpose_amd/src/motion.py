@@ -252,6 +252,81 @@ def Batch_hand_extraction(videopath, motiondata, recpoints, outpath, *, hand, ba
     return None
 
 
+def _fast_mode_pass(videopath, outpath, batch_size, capture, joints, rows_of):
+    """What the reference's fast-mode body pass does around its model call
+    (srcmx/Batch_motion_Estimation.py:68-113): a file that does not open is reported and yields
+    None; one row of `joints` keypoints per frame the container reports, filled batch by batch
+    with rows_of(frames [n, H, W, 3]) -> [n, joints, 3]; its progress prints, joblib.dump, its
+    closing print.  Frames past the reported count are not read (the reference's DataLoader goes
+    by len()); a container that reports more frames than decode ends as the reference's data
+    loader does, slicing the None a failed read returns (srcmx/Batch_model.py:47-49)."""
+    import itertools
+    import os
+    video = VideoFrames(videopath, capture=capture)
+    if not video.opened:
+        print('the file %s is not exist' % videopath)
+        return None
+    COUNTS = len(video)
+    outname = os.path.split(outpath)[1]
+    MotionMat = np.zeros((COUNTS, joints, 3))
+    count = 0
+    for frames in _batches(itertools.islice(video, COUNTS), None, batch_size):
+        n = len(frames)
+        MotionMat[count:count + n] = rows_of(np.stack(frames))
+        for c in range(count + 1, count + n + 1):
+            if c % 1000 == 0:
+                print('%s-%d/%d' % (outname, c, COUNTS))
+        count += n
+    if count < COUNTS:
+        raise TypeError("'NoneType' object is not subscriptable")
+    import joblib
+    joblib.dump(MotionMat, outpath)
+    print('the %s file is saved' % outpath)
+    return None
+
+
+def Batch_body_extraction(videopath, outpath, batch_size, recpoint, *, body, capture=None):
+    """The reference's fast-mode body pass (srcmx/Batch_motion_Estimation.py:68-113) on the GPU:
+    the video's frames cut to recpoint [(x0, y0), (x1, y1)] -> MotionMat [T, 18, 3] (T = the
+    container's frame count; per frame the person with the largest left-shoulder x), written to
+    `outpath` with joblib.dump.  Returns None, like the reference; a video that does not open is
+    reported on stdout and nothing is written.  body: a src.batch_model.Batch_body (the reference's
+    module-level Batch_Body_model); each batch of frames is one Batch_body.extract, the region of
+    interest applied as an offset into the whole frames.  capture: see VideoFrames."""
+    return _fast_mode_pass(videopath, outpath, batch_size, capture, 18, lambda frames: body.extract(frames, recpoint))
+
+
+def Batch_motion_extraction(videopath, outpath, batch_size, recpoint, *, body, hand, capture=None):
+    """Both fast-mode passes of the reference (Batch_body_extraction, then Batch_hand_extraction
+    on its poses, srcmx/Batch_motion_Estimation.py:19-113) in one pass over the video: MotionMat
+    [T, 60, 3], body rows 0-17, left hand 18-38, right hand 39-59, written like
+    Batch_body_extraction's.  Per batch the frames are uploaded once, Batch_body.extract_device's
+    poses feed Batch_hand.extract_device (boxsize 368) on the device, and the [n, 60, 3] rows and
+    the statuses come back in one download each; the two handles are ordered through torch's
+    current stream.  A batch in which a frame overflows the body record capacity runs again
+    through Batch_body.extract, which grows the capacity; other statuses raise what
+    Batch_body.extract / Batch_hand.extract raise."""
+    import torch
+    from . import _native
+    devc = torch.device("cuda", body.handle.device)
+
+    def rows_of(frames):
+        dev = torch.from_numpy(frames).to(devc)
+        pose, bstat = body.extract_device(dev, recpoint)
+        handmat, hstat = hand.extract_device(dev, pose, 368, recpoint)
+        rows = torch.cat([pose, handmat], 1).cpu().numpy()
+        bstat, hstat = bstat.cpu().numpy(), hstat.cpu().numpy()
+        if (bstat == _native.OPOSE_E_CAPACITY).any():
+            pose = body.extract(dev, recpoint)
+            return np.concatenate([pose, hand.extract(dev, pose, 368, recpoint)], 1)
+        for s in bstat:
+            _native.raise_record_status(int(s), body.peaks_per_part, body.max_people)
+        hand.raise_status(hstat)
+        return rows
+
+    return _fast_mode_pass(videopath, outpath, batch_size, capture, 60, rows_of)
+
+
 def Extract_MotionData_from_Video(videopath, outpath, Recpoint, mode="body", overwrite=False, *, body, hand=None,
                                   batch=32, device=None, capture=None):
     """The reference's entry point (srcmx/MotionEstimation.py:25-76) on the GPU Body / Hand:

@@ -14,6 +14,24 @@ import numpy as np
 from . import util
 
 
+def selected_pose(candidate, subset) -> np.ndarray:
+    """The PoseMat row [18, 3] `Batch_body_extraction` keeps of a frame's (candidate, subset)
+    (srcmx/Batch_motion_Estimation.py:88-107): the 18 keypoints (x, y, score) of the person with
+    the largest left-shoulder x, zeros where a keypoint is missing or nobody was found.  The host
+    statement of what `Body.poses` / `Batch_body.extract` compute on the device."""
+    pose = np.zeros((18, 3))
+    if len(subset) >= 1:
+        shoulder_x = np.zeros((len(subset),))
+        for person in range(len(subset)):
+            shoulder_x[person] = candidate[int(subset[person][5])][0]
+        best = np.argmax(shoulder_x)
+        for part in range(18):
+            idx = int(subset[best][part])
+            if idx != -1:
+                pose[part, :] = candidate[idx][:3]
+    return pose
+
+
 def motion_data_every_frame(body, hand, oriImg, mode: str = "body") -> np.ndarray:
     candidate, subset = body(oriImg)
     pose = np.zeros((60, 3))
