@@ -23,7 +23,7 @@ import numpy as np
 from . import _native
 from ._native import lib
 from .body import Body
-from .hand import _as_reference_array, hand_outputs
+from .hand import _as_reference_array, hand_boxes, hand_outputs, pose_rows
 from .model import handpose_model, load_model
 
 
@@ -169,24 +169,13 @@ class Batch_hand(object):
     # Batch_hand_extraction (srcmx/Batch_motion_Estimation.py:29-60) on the device
     _frames_view = staticmethod(_frames_view)
 
-    @staticmethod
-    def _motion(motion, N):
-        if hasattr(motion, "cpu"):
-            motion = motion.cpu().numpy()
-        motion = np.ascontiguousarray(motion, dtype=np.float64)
-        if motion.shape != (N, 18, 3):
-            raise ValueError("expected one body pose [18, 3] per frame: motion [%d, 18, 3]" % N)
-        return motion
+    _motion = staticmethod(pose_rows)
 
     def boxes(self, motion, hw):
         """HandImageDataset's utilmx.handDetect call (srcmx/Batch_model.py:74-84) for N poses
         motion [N, 18, 3] in frames of hw = (H, W): int32 [N, 2, 4] = {x, y, w, present}, left
         then right; an absent side is zeros."""
-        motion = self._motion(motion, len(motion))
-        boxes = np.empty((len(motion), 2, 4), np.int32)
-        self.handle.check(lib.opose_batch_hand_boxes(self.handle.h, motion.ctypes.data, len(motion), int(hw[0]),
-                                                     int(hw[1]), boxes.ctypes.data, 0))
-        return boxes
+        return hand_boxes(self.handle, motion, hw)
 
     @staticmethod
     def _raise_empty(bad):

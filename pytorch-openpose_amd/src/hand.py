@@ -36,6 +36,27 @@ def _as_reference_array(peaks: np.ndarray, found: np.ndarray) -> np.ndarray:
     return out
 
 
+def pose_rows(motion, N):
+    """Body poses as the hand entry points take them: float64 [N, 18, 3], C-contiguous."""
+    if hasattr(motion, "cpu"):
+        motion = motion.cpu().numpy()
+    motion = np.ascontiguousarray(motion, dtype=np.float64)
+    if motion.shape != (N, 18, 3):
+        raise ValueError("expected one body pose [18, 3] per frame: motion [%d, 18, 3]" % N)
+    return motion
+
+
+def hand_boxes(handle, motion, hw):
+    """utilmx.handDetect (srcmx/utilmx.py:267-327; src/util.py:133-201 is the same arithmetic) on the
+    device for N poses motion [N, 18, 3] in frames of hw = (H, W): int32 [N, 2, 4] = {x, y, w,
+    present}, left then right; an absent side is zeros."""
+    motion = pose_rows(motion, len(motion))
+    boxes = np.empty((len(motion), 2, 4), np.int32)
+    handle.check(_native.lib.opose_batch_hand_boxes(handle.h, motion.ctypes.data, len(motion), int(hw[0]), int(hw[1]),
+                                                    boxes.ctypes.data, 0))
+    return boxes
+
+
 class Hand(object):
     def __init__(self, model_path, device: int = 0, scale_search=(0.5, 1.0, 1.5, 2.0), boxsize=368, stride=8,
                  padValue=128, thre=0.03):
@@ -76,6 +97,13 @@ class Hand(object):
         self.handle.check(_native.lib.opose_hand_infer_crops(self.handle.h, ptrs, sizes.ctypes.data, strides.ctypes.data,
                                                              n, self.params, peaks.ctypes.data, found.ctypes.data, 0))
         return [_as_reference_array(peaks[i], found[i]) for i in range(n)]
+
+    def boxes(self, motion, hw):
+        """util.handDetect (src/util.py:133-201) on the device for N poses motion [N, 18, 3] (the rows
+        Body.poses gives) in frames of hw = (H, W): int32 [N, 2, 4] = {x, y, w, present}, left then
+        right; an absent side is zeros.  The crops MotionData_every_frame cuts for Hand
+        (srcmx/MotionEstimation.py:186-201) are frame[y:y+w, x:x+w]."""
+        return hand_boxes(self.handle, motion, hw)
 
     def post(self, maps, pads, H, W):
         """Post-network path only (src/hand.py:51-75).
