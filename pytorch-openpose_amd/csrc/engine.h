@@ -25,13 +25,9 @@
 #include "../../include/opose.h"
 #include "common.h"
 #include "kernels.h"
+#include "topology.h"
 
 namespace opose {
-
-struct Spec {
-    std::string name;
-    int cin, cout, ks, pad;
-};
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -122,6 +118,17 @@ struct DevConv {
         if (bias) (void)hipFree(bias);
         if (ktab) (void)hipFree(ktab);
     }
+};
+
+// The DevConv of every step of a forward (topology.h NetDesc), resolved once by
+// opose_load_weights: pointers into opose_ctx::convs[net].
+struct NetTable {
+    std::vector<DevConv*> trunk;
+    struct Stage {
+        DevConv* open = nullptr;       // the opening layer, every branch in one conv (null: none)
+        std::vector<DevConv*> mid[2];  // per branch
+        DevConv* close[2][2] = {};     // per branch the closing 1x1 pair (a missing branch: null)
+    } stages[kStages];
 };
 
 struct ProfEntry {
@@ -261,11 +268,9 @@ struct Redirect {
 bool env_flag(const char* name, bool dflt);  // a boolean switch: "0" / "1" first character, else dflt
 hipError_t pooled_stream(hipStream_t* s, int priority);
 // engine_weights.cpp
-std::vector<Spec> vgg_body();
-std::vector<Spec> vgg_hand();
-DevConv* find_conv(opose_ctx* h, int net, const std::string& name);
+// lvl, pair: DevConv::lvl / pair (a layer outside the networks: 3, false)
 void upload_conv(opose_ctx* h, int net, const std::string& key, const std::vector<const Spec*>& parts,
-                 const std::vector<const float*>& w, const std::vector<const float*>& b,
+                 const std::vector<const float*>& w, const std::vector<const float*>& b, int lvl, bool pair,
                  const std::vector<int>& cmap = {});
 // engine_plan.cpp
 TileChoice choose_tile(int Mpad, const std::vector<int>& gpix, int nK, bool x6 = false, bool dp_only = false,
@@ -278,10 +283,8 @@ XAct x6act(uint8_t* p, int cg, int goff, int N, int H, int W);
 size_t x6p_plane(int N, int H, int W);
 XAct x6pact(uint8_t* p, int cg, int goff, int N, int H, int W);
 void run_conv_x6_segs(opose_ctx* h, const std::vector<ConvSeg>& segs, bool pool = false);
-std::vector<float*> body_net_x6(opose_ctx* h, const std::vector<NetSeg>& segs, const Band* band = nullptr);
-std::vector<float*> hand_net_x6(opose_ctx* h, const std::vector<NetSeg>& segs);
-float* body_net(opose_ctx* h, const float* x, int N, int Hp, int Wp);
-float* hand_net(opose_ctx* h, const float* x, int N, int Hp, int Wp);
+std::vector<float*> net_forward_x6(opose_ctx* h, int net, const std::vector<NetSeg>& segs, const Band* band = nullptr);
+float* net_forward(opose_ctx* h, int net, const float* x, int N, int Hp, int Wp);
 // engine_post.cpp
 ScaleGeom geom(double s, const opose_params& p, int H, int W);
 ScaleGeom geom_from_pads(int hl, int wl, int pad_down, int pad_right, int H, int W);
@@ -339,6 +342,7 @@ struct opose_ctx {
     int ppp = 128, maxp = 96;
     // weights
     std::map<std::string, std::unique_ptr<opose::DevConv>> convs[2];
+    opose::NetTable table[2];  // valid while loaded[net]
     bool loaded[2] = {false, false};
     // workspace
     // network convolutions: fp32-accurate split-bf16 kernel (default) or the fp32 MFMA kernel

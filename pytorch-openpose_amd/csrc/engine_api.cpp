@@ -204,23 +204,29 @@ static void run_scales_concurrently(opose_ctx* h, int ns, const std::function<vo
     for (int s = 1; s < ns; ++s) OPOSE_HIP_CHECK(hipStreamWaitEvent(main, h->ev_join[s], 0));
 }
 
+// One scale's frames preprocessed into the network input of workspace set `slot`
+static float* preprocess_into(opose_ctx* h, int slot, const uint8_t* fd, int64_t frame_stride, int64_t row_stride, int N,
+                              int H, int W, const ScaleGeom& g, const opose_params& p) {
+    float* x = h->ws[slot].x.ensure<float>((size_t)N * 3 * g.Hp * g.Wp, h->stream);
+    ProfEntry pe;
+    h->prof_begin(pe, "preprocess", 0, (double)N * (3.0 * H * W + 12.0 * g.Hp * g.Wp));
+    preprocess_scale(fd, frame_stride, row_stride, N, H, W, g, p, x, h->stream);
+    h->prof_end(pe);
+    return x;
+}
+
 // Every scale's network in lockstep on the handle's stream (split-bf16 path): per scale the
-// preprocess into its slot's input, one conv launch per layer for all scales (hand_net_x6 /
-// body_net_x6 segments), per scale the x8 upsample of its C heat / PAF channels into mid(s).
+// preprocess into its slot's input, one conv launch per layer for all scales (net_forward_x6
+// segments), per scale the x8 upsample of its C heat / PAF channels into mid(s).
 static void run_scales_lockstep(opose_ctx* h, int net, const uint8_t* fd, int64_t frame_stride, int64_t row_stride,
                                 int N, int H, int W, const std::vector<ScaleGeom>& gs, const opose_params& p) {
     if (!h->loaded[net]) throw std::runtime_error(net == OPOSE_NET_BODY ? "body weights not loaded" : "hand weights not loaded");
     std::vector<NetSeg> segs;
     for (size_t s = 0; s < gs.size(); ++s) {
-        const ScaleGeom& g = gs[s];
-        float* x = h->ws[s].x.ensure<float>((size_t)N * 3 * g.Hp * g.Wp, h->stream);
-        ProfEntry pe;
-        h->prof_begin(pe, "preprocess", 0, (double)N * (3.0 * H * W + 12.0 * g.Hp * g.Wp));
-        preprocess_scale(fd, frame_stride, row_stride, N, H, W, g, p, x, h->stream);
-        h->prof_end(pe);
-        segs.push_back(NetSeg{x, N, g.Hp, g.Wp, (int)s});
+        float* x = preprocess_into(h, (int)s, fd, frame_stride, row_stride, N, H, W, gs[s], p);
+        segs.push_back(NetSeg{x, N, gs[s].Hp, gs[s].Wp, (int)s});
     }
-    const std::vector<float*> outs = net == OPOSE_NET_BODY ? body_net_x6(h, segs) : hand_net_x6(h, segs);
+    const std::vector<float*> outs = net_forward_x6(h, net, segs);
     for (size_t s = 0; s < gs.size(); ++s)
         if (net == OPOSE_NET_BODY)
             body_to_mid(h, (int)s, outs[s], 185, N, gs[s]);
@@ -292,7 +298,7 @@ static size_t band_halo_bytes(int wl) { return (size_t)3 * 32 * 3 * x6p_pitch(wl
 
 using namespace opose;
 
-static int net_forward(opose_t* h, int net, const float* x, int N, int Hp, int Wp, float* o1, float* o2, int flags) {
+static int forward_to_caller(opose_t* h, int net, const float* x, int N, int Hp, int Wp, float* o1, float* o2, int flags) {
     if (!h || !x || N <= 0 || Hp < 8 || Wp < 8 || Hp % 8 || Wp % 8) return OPOSE_E_ARG;
     OPOSE_TRY(h, {
         enter_main(h);
@@ -306,16 +312,13 @@ static int net_forward(opose_t* h, int net, const float* x, int N, int Hp, int W
         const int hl = Hp / 8, wl = Wp / 8;
         const size_t plane = (size_t)hl * wl;
         const hipMemcpyKind kind = (flags & OPOSE_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (net == OPOSE_NET_BODY) {
-            float* S = body_net(h, xd, N, Hp, Wp);
-            // S: [N][185][hl][wl]; paf = ch 0..37, heat = 38..56
-            OPOSE_HIP_CHECK(hipMemcpy2DAsync(o1, 38 * plane * 4, S, 185 * plane * 4, 38 * plane * 4, N, kind, h->stream));
-            OPOSE_HIP_CHECK(hipMemcpy2DAsync(o2, 19 * plane * 4, S + 38 * plane, 185 * plane * 4, 19 * plane * 4, N,
-                                             kind, h->stream));
-        } else {
-            float* S = hand_net(h, xd, N, Hp, Wp);
-            OPOSE_HIP_CHECK(hipMemcpy2DAsync(o1, 22 * plane * 4, S, 150 * plane * 4, 22 * plane * 4, N, kind, h->stream));
-        }
+        // S: [N][Sc][hl][wl], branch b's maps from channel s_off[b] (body: paf, heat; hand: heat)
+        const NetDesc& d = net_desc(net);
+        float* S = net_forward(h, net, xd, N, Hp, Wp);
+        float* const outs[2] = {o1, o2};
+        for (int b = 0; b < d.branches; ++b)
+            OPOSE_HIP_CHECK(hipMemcpy2DAsync(outs[b], d.bout[b] * plane * 4, S + d.s_off[b] * plane, d.Sc * plane * 4,
+                                             d.bout[b] * plane * 4, N, kind, h->stream));
         if (!(flags & OPOSE_OUT_DEVICE)) OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
         h->prof_drain();
     });
@@ -344,12 +347,12 @@ int opose_hand_forward_pyramid(opose_t* h, int n, const float* const* xs, const 
         }
         std::vector<float*> outs;
         if (h->x6) {
-            outs = hand_net_x6(h, segs);
+            outs = net_forward_x6(h, OPOSE_NET_HAND, segs);
         } else {
             Redirect<int> slot(h->slot);
             for (int i = 0; i < n; ++i) {
                 h->slot = i;
-                outs.push_back(hand_net(h, segs[i].x, N[i], Hp[i], Wp[i]));
+                outs.push_back(net_forward(h, OPOSE_NET_HAND, segs[i].x, N[i], Hp[i], Wp[i]));
             }
         }
         for (int i = 0; i < n; ++i) {
@@ -365,12 +368,12 @@ int opose_hand_forward_pyramid(opose_t* h, int n, const float* const* xs, const 
 
 int opose_body_forward(opose_t* h, const float* x, int N, int Hp, int Wp, float* paf, float* heat, int flags) {
     if (!paf || !heat) return OPOSE_E_ARG;
-    return net_forward(h, OPOSE_NET_BODY, x, N, Hp, Wp, paf, heat, flags);
+    return forward_to_caller(h, OPOSE_NET_BODY, x, N, Hp, Wp, paf, heat, flags);
 }
 
 int opose_hand_forward(opose_t* h, const float* x, int N, int Hp, int Wp, float* heat, int flags) {
     if (!heat) return OPOSE_E_ARG;
-    return net_forward(h, OPOSE_NET_HAND, x, N, Hp, Wp, heat, nullptr, flags);
+    return forward_to_caller(h, OPOSE_NET_HAND, x, N, Hp, Wp, heat, nullptr, flags);
 }
 
 int opose_body_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride, int64_t frame_stride,
@@ -386,12 +389,8 @@ int opose_body_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_
         uint8_t* rec = records_dest(h, N, records, flags);
         auto scale_net = [&](int s) {
             const ScaleGeom& g = gs[s];
-            float* x = h->w().x.ensure<float>((size_t)N * 3 * g.Hp * g.Wp, h->stream);
-            ProfEntry pe;
-            h->prof_begin(pe, "preprocess", 0, (double)N * (3.0 * H * W + 12.0 * g.Hp * g.Wp));
-            preprocess_scale(fd, frame_stride, row_stride, N, H, W, g, p, x, h->stream);
-            h->prof_end(pe);
-            float* S = body_net(h, x, N, g.Hp, g.Wp);
+            float* x = preprocess_into(h, h->slot, fd, frame_stride, row_stride, N, H, W, g, p);
+            float* S = net_forward(h, OPOSE_NET_BODY, x, N, g.Hp, g.Wp);
             body_to_mid(h, s, S, 185, N, g);
         };
         const bool lockstep = h->x6 && h->lockstep && p.n_scales > 1;
@@ -469,7 +468,7 @@ int opose_body_scale_maps(opose_t* h, const uint8_t* bgr, int N, int H, int W, i
         const ScaleGeom g = geom(p.scales[s], p, H, W);
         float* x = h->w().x.ensure<float>((size_t)N * 3 * g.Hp * g.Wp, h->stream);
         preprocess_scale(fd, frame_stride, row_stride, N, H, W, g, p, x, h->stream);
-        const float* S = body_net(h, x, N, g.Hp, g.Wp);
+        const float* S = net_forward(h, OPOSE_NET_BODY, x, N, g.Hp, g.Wp);
         // channels 0..56 of the stage-6 concat buffer [N][185][hl*wl] -> [N][57][hl*wl]
         const size_t plane = (size_t)g.hl * g.wl * 4;
         OPOSE_HIP_CHECK(hipMemcpy2DAsync(maps, 57 * plane, S, 185 * plane, 57 * plane, N,
@@ -505,7 +504,7 @@ int opose_body_band_maps(opose_t* h, const uint8_t* bgr, int H, int W, int64_t r
         preprocess_scale(fd, row_stride * H, row_stride, 1, H, W, g, p, x, h->stream);
         const size_t cap = xbuf_bytes / 4;
         const Band band{r0, r1, out, fn, user, static_cast<uint8_t*>(xbuf), cap};
-        body_net_x6(h, {NetSeg{x, 1, g.Hp, g.Wp, h->slot}}, &band);
+        net_forward_x6(h, OPOSE_NET_BODY, {NetSeg{x, 1, g.Hp, g.Wp, h->slot}}, &band);
         if (!(flags & OPOSE_OUT_DEVICE)) {
             OPOSE_HIP_CHECK(hipMemcpyAsync(maps, out, (size_t)57 * hb * g.wl * 4, hipMemcpyDeviceToHost, h->stream));
             OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -561,7 +560,7 @@ static uint8_t* run_batch_body(opose_ctx* h, const uint8_t* bgr, int N, int H, i
         const float sc = (float)(1.0 / scale);  // torch: float(1 / scale_factor)
         launch_preprocess_torch(fd, frame_stride, row_stride, N, H, W, nh, nw, sc, sc, Hp, Wp, x, h->stream);
         h->prof_end(pe);
-        float* S = body_net(h, x, N, Hp, Wp);
+        float* S = net_forward(h, OPOSE_NET_BODY, x, N, Hp, Wp);
         batch_post_common(h, N, H, W, S, 185, Hp / 8, Wp / 8, nh, nw, p, rec);
     });
     return rec;
@@ -611,12 +610,8 @@ int opose_hand_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_
             call_key("hand", N, H, W, row_stride, frame_stride, p, fd, od ? (const void*)peaks : nullptr, 0, 0) + fk;
         auto scale_net = [&](int s) {
             const ScaleGeom& g = gs[s];
-            float* x = h->w().x.ensure<float>((size_t)N * 3 * g.Hp * g.Wp, h->stream);
-            ProfEntry pe;
-            h->prof_begin(pe, "preprocess", 0, (double)N * (3.0 * H * W + 12.0 * g.Hp * g.Wp));
-            preprocess_scale(fd, frame_stride, row_stride, N, H, W, g, p, x, h->stream);
-            h->prof_end(pe);
-            float* Sb = hand_net(h, x, N, g.Hp, g.Wp);
+            float* x = preprocess_into(h, h->slot, fd, frame_stride, row_stride, N, H, W, g, p);
+            float* Sb = net_forward(h, OPOSE_NET_HAND, x, N, g.Hp, g.Wp);
             upsample_to_mid(h, s, Sb, 150, N, g, 21);
         };
         if (h->x6 && h->lockstep && p.n_scales > 1) {
@@ -666,7 +661,7 @@ int opose_batch_hand_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, 
         h->prof_begin(pe, "preprocess", 0, (double)N * 15.0 * H * W);
         launch_preprocess_torch(fd, frame_stride, row_stride, N, H, W, H, W, 1.f, 1.f, H, W, x, h->stream);
         h->prof_end(pe);
-        float* Sb = hand_net(h, x, N, H, W);
+        float* Sb = net_forward(h, OPOSE_NET_HAND, x, N, H, W);
         batch_hand_post_common(h, N, H, W, Sb, 150, p, peaks, found, flags);
     });
     return OPOSE_OK;
@@ -784,7 +779,7 @@ int opose_batch_hand_extract(opose_t* h, const uint8_t* bgr, int N, int H, int W
         const int chunk = h->extract_chunk > 0 ? std::min(h->extract_chunk, fit) : fit;
         for (int c0 = 0; c0 < slots; c0 += chunk) {
             const int nc = std::min(chunk, slots - c0);
-            float* Sb = hand_net(h, x + (size_t)c0 * per_crop, nc, bs, bs);
+            float* Sb = net_forward(h, OPOSE_NET_HAND, x + (size_t)c0 * per_crop, nc, bs, bs);
             batch_hand_post_common(h, nc, bs, bs, Sb, 150, p, peaks + (size_t)c0 * 63, found + (size_t)c0 * 21,
                                    OPOSE_OUT_DEVICE);
         }
@@ -927,11 +922,11 @@ int opose_hand_infer_crops(opose_t* h, const uint8_t* const* crops, const int* s
                     segs.push_back(NetSeg{x, nc, g0.Hp, g0.Wp, s});
                     continue;
                 }
-                float* Sb = hand_net(h, x, nc, g0.Hp, g0.Wp);
+                float* Sb = net_forward(h, OPOSE_NET_HAND, x, nc, g0.Hp, g0.Wp);
                 upsample_to_mid(h, s, Sb, 150, nc, g0, 21);
             }
             if (lockstep) {
-                const std::vector<float*> outs = hand_net_x6(h, segs);
+                const std::vector<float*> outs = net_forward_x6(h, OPOSE_NET_HAND, segs);
                 for (int s = 0; s < ns; ++s) upsample_to_mid(h, s, outs[s], 150, nc, gs[0][s], 21);
             }
             for (int i = c0; i < c0 + nc; ++i)

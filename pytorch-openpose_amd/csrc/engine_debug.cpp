@@ -10,7 +10,7 @@ int opose_debug_conv(opose_t* h, const float* x, const float* w, const float* b,
     OPOSE_TRY(h, {
         enter_main(h);
         Spec s{"debug", Cin, Cout, ks, pad};
-        upload_conv(h, 0, "__debug__", {&s}, {w}, {b});
+        upload_conv(h, 0, "__debug__", {&s}, {w}, {b}, 3, false);
         DevConv* c = h->convs[0]["__debug__"].get();
         DevBuf xin, yout;
         const size_t nx = (size_t)N * Cin * H * W, ny = (size_t)N * Cout * H * W;
@@ -69,7 +69,7 @@ int opose_debug_conv_x6(opose_t* h, const float* x, const float* w, const float*
     OPOSE_TRY(h, {
         enter_main(h);
         Spec s{"debug", Cin, Cout, ks, pad};
-        upload_conv(h, 0, "__debug__", {&s}, {w}, {b});
+        upload_conv(h, 0, "__debug__", {&s}, {w}, {b}, 3, false);
         DevConv* c = h->convs[0]["__debug__"].get();
         const int HW = H * W;
         const int cg = c->cin_g, og = (Cout + 7) / 8;
@@ -169,7 +169,7 @@ int opose_debug_conv_x6_time(opose_t* h, int N, int Cin, int H, int W, int Cout,
         Spec s{"timing", Cin, Cout, ks, ks / 2};
         std::vector<float> w((size_t)Cout * Cin * ks * ks), b(Cout, 0.f);
         for (size_t i = 0; i < w.size(); ++i) w[i] = (float)((i * 2654435761u) % 2001) / 1000.f - 1.f;
-        upload_conv(h, 0, "__timing__", {&s}, {w.data()}, {b.data()});
+        upload_conv(h, 0, "__timing__", {&s}, {w.data()}, {b.data()}, 3, false);
         DevConv* c = h->convs[0]["__timing__"].get();
         const int HW = H * W;
         const int cg = c->cin_g, og = (Cout + 7) / 8;
@@ -220,7 +220,7 @@ int opose_debug_conv_time(opose_t* h, int N, int Cin, int H, int W, int Cout, in
         enter_main(h);
         Spec s{"timing", Cin, Cout, ks, ks / 2};
         std::vector<float> w((size_t)Cout * Cin * ks * ks, 0.01f), b(Cout, 0.f);
-        upload_conv(h, 0, "__timing__", {&s}, {w.data()}, {b.data()});
+        upload_conv(h, 0, "__timing__", {&s}, {w.data()}, {b.data()}, 3, false);
         DevConv* c = h->convs[0]["__timing__"].get();
         launch_fill_hash(c->wt, (size_t)c->Kpad * c->Mpad, 7, h->stream);
         DevBuf xin, yout;

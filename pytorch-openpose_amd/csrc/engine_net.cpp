@@ -1,15 +1,21 @@
-// engine_net.cpp — network drivers of libopose: the fp32 and the split-bf16 (X6) forward of the body
-// and hand networks, one conv launch per layer over every segment.
+// engine_net.cpp — network drivers of libopose: one walk over a network's description (topology.h)
+// and its two executors, the fp32 and the split-bf16 (X6) forward, one conv launch per layer over
+// every segment.
 #include "engine.h"
 
 namespace opose {
 
-// OPOSE_PIPELINE_DEFER gate: the layer before which the next network records it ("stageN": before
-// CPM stage N).  Swept on the bench, same box: conv4_1 2,101, stage2 2,100, stage3 2,105, stage4
-// 2,107 frames/s against 2,110 with no gate (a round-4 A/B, kept in git history)
-static const std::string& gate_layer() {
-    static const std::string g = "conv3_1";
-    return g;
+// the network's layers as opose_load_weights resolved them
+static const NetTable& net_table(opose_ctx* h, int net) {
+    if (!h->loaded[net]) throw std::runtime_error(std::string(net_desc(net).what) + " weights not loaded");
+    return h->table[net];
+}
+
+// OPOSE_PIPELINE_DEFER (NetDesc::gate): the previous call's post-network part may start
+static void record_gate(opose_ctx* h) {
+    if (!h->gate_ev) return;
+    OPOSE_HIP_CHECK(hipEventRecord(h->gate_ev, h->stream));
+    h->gate_done = true;
 }
 
 static const char* conv_class(int ks) { return ks == 7 ? "conv7x7" : (ks == 3 ? "conv3x3" : "conv1x1"); }
@@ -79,16 +85,17 @@ static void run_pool(opose_ctx* h, const float* in, float* out, int NC, int H, i
 }
 
 // VGG trunk: x [N,3,H,W] -> final trunk conv written via `last` (+ optional duplicate)
-static void run_trunk(opose_ctx* h, int net, const float* x, int N, int H, int W, Act last, Act dup) {
-    const std::vector<Spec> vgg = net == OPOSE_NET_BODY ? vgg_body() : vgg_hand();
+static void run_trunk(opose_ctx* h, const NetDesc& d, const NetTable& t, const float* x, int N, int H, int W, Act last,
+                      Act dup) {
+    const std::vector<Layer>& vgg = d.trunk;
     size_t act = (size_t)N * 64 * H * W;
     float* A = h->w().bufA.ensure<float>(act, h->stream);
     float* B = h->w().bufB.ensure<float>(act, h->stream);
     const float* cur = x;
     int cc = 3, hh = H, ww = W;
     for (size_t i = 0; i < vgg.size(); ++i) {
-        const Spec& s = vgg[i];
-        DevConv* c = find_conv(h, net, s.name);
+        const Spec& s = vgg[i].s;
+        DevConv* c = t.trunk[i];
         const bool final_layer = i + 1 == vgg.size();
         float* dst = (cur == A) ? B : A;
         Act out = final_layer ? last : Act{dst, s.cout, 0};
@@ -96,8 +103,7 @@ static void run_trunk(opose_ctx* h, int net, const float* x, int N, int H, int W
                  final_layer ? dup : Act{nullptr, 0, 0});
         cur = dst;
         cc = s.cout;
-        // pools follow conv1_2, conv2_2, conv3_4 (src/model.py:37,40,45 / :147,150,155)
-        if (s.name == "conv1_2" || s.name == "conv2_2" || s.name == "conv3_4") {
+        if (vgg[i].pool) {  // (src/model.py:37,40,45 / :147,150,155)
             float* pd = (cur == A) ? B : A;
             run_pool(h, cur, pd, N * cc, hh, ww);
             hh /= 2;
@@ -154,6 +160,14 @@ static XAct frame_view(const XAct& a, int n, int H, int W) {
     return v;
 }
 
+// "layer/<names>" of a launch's profiler detail: the first segment's layer and every other one
+static std::string layer_names(const std::vector<ConvSeg>& segs) {
+    std::string nm = segs[0].c->name;
+    for (size_t g = 1; g < segs.size(); ++g)
+        if (segs[g].c != segs[0].c && nm.find(segs[g].c->name) == std::string::npos) nm += "|" + segs[g].c->name;
+    return "layer/" + nm;
+}
+
 // One launch: segments of one kernel family, at most kX6Groups of them, slab counts set.
 static void launch_segs(opose_ctx* h, const std::vector<ConvSeg>& segs, int family, bool pool) {
     const bool win = family == kKernelWin, wino = family == kKernelWino;
@@ -208,12 +222,7 @@ static void launch_segs(opose_ctx* h, const std::vector<ConvSeg>& segs, int fami
     if (wino) {
         ProfEntry pe;
         h->prof_begin(pe, conv_class(c0->ks), flops, 0);
-        if (h->detail) {
-            std::string nm = c0->name;
-            for (int g = 1; g < ng; ++g)
-                if (segs[g].c != c0 && nm.find(segs[g].c->name) == std::string::npos) nm += "|" + segs[g].c->name;
-            pe.detail = "layer/" + nm + "/wino/g" + std::to_string(ng) + "/n" + std::to_string(npix_all);
-        }
+        if (h->detail) pe.detail = layer_names(segs) + "/wino/g" + std::to_string(ng) + "/n" + std::to_string(npix_all);
         launch_conv_wino_x6(a, h->stream);
         h->prof_end(pe);
         return;
@@ -225,14 +234,10 @@ static void launch_segs(opose_ctx* h, const std::vector<ConvSeg>& segs, int fami
     a.partial = num.units != num.tiles ? h->w().partial.ensure<float>((size_t)num.units * p.mt * p.pt, h->stream) : nullptr;
     ProfEntry pe;
     h->prof_begin(pe, conv_class(c0->ks), flops, 0);
-    if (h->detail) {
-        std::string nm = c0->name;
-        for (int g = 1; g < ng; ++g)
-            if (segs[g].c != c0 && nm.find(segs[g].c->name) == std::string::npos) nm += "|" + segs[g].c->name;
-        pe.detail = "layer/" + nm + "/" + (win ? "win" : "x6") + "/" + std::to_string(p.mt) + "x" + std::to_string(p.pt) +
+    if (h->detail)
+        pe.detail = layer_names(segs) + "/" + (win ? "win" : "x6") + "/" + std::to_string(p.mt) + "x" + std::to_string(p.pt) +
                     "g" + std::to_string(p.grid) + "u" + std::to_string(num.units) + "/g" + std::to_string(ng) + "/n" +
                     std::to_string(npix_all);
-    }
     if (win) launch_conv_win_x6(a, h->stream);
     else launch_conv_x6(a, p.mt, p.pt, h->stream);
     h->prof_end(pe);
@@ -396,23 +401,17 @@ static void clear_x6p_pads(opose_ctx* h, std::initializer_list<std::pair<DevBuf*
 // (+ dup[i]).  Full and half resolution run on dense X6 buffers (A / B); from the second pool on
 // (H/4: conv3_x, H/8: conv4_x, conv5_x of the hand) the activations are padded X6P (P0 / P1,
 // Q0 / Q1), which the windowed conv_win_x6 reads (conv_x6 reads either layout).
-static void run_trunk_x6(opose_ctx* h, int net, const std::vector<NetSeg>& segs, const std::vector<XAct>& last,
-                         const std::vector<XAct>& dup) {
-    const std::vector<Spec> vgg = net == OPOSE_NET_BODY ? vgg_body() : vgg_hand();
+static void run_trunk_x6(opose_ctx* h, const NetDesc& d, const NetTable& t, const std::vector<NetSeg>& segs,
+                         const std::vector<XAct>& last, const std::vector<XAct>& dup) {
+    const std::vector<Layer>& vgg = d.trunk;
     const size_t ns = segs.size();
     // padded levels (fused pooling only: the separate maxpool_x6 reads and writes dense X6)
     const bool padded = h->fused_pool;
     int maxg4 = 0, maxg8 = 0;  // widest activation (groups) at H/4 and H/8
-    {
-        int lvl = 0;
-        for (const Spec& s : vgg) {
-            const int og = (s.cout + 7) / 8;
-            const bool pooled = s.name == "conv1_2" || s.name == "conv2_2" || s.name == "conv3_4";
-            const int out_lvl = lvl + (pooled ? 1 : 0);
-            if (out_lvl == 2) maxg4 = std::max(maxg4, og);
-            if (out_lvl == 3) maxg8 = std::max(maxg8, og);
-            lvl = out_lvl;
-        }
+    for (const Layer& L : vgg) {
+        const int og = (L.s.cout + 7) / 8, out_lvl = L.lvl + (L.pool ? 1 : 0);
+        if (out_lvl == 2) maxg4 = std::max(maxg4, og);
+        if (out_lvl == 3) maxg8 = std::max(maxg8, og);
     }
     struct Bufs {
         uint8_t *A, *B, *P0, *P1, *Q0, *Q1;
@@ -464,8 +463,8 @@ static void run_trunk_x6(opose_ctx* h, int net, const std::vector<NetSeg>& segs,
     };
     // conv1_2 + pool with the input window in LDS instead of the 9-tap im2col stream (segment i,
     // input at resolution level lvl)
-    auto conv12_win_ok = [&](const Spec& s, const DevConv* c) {
-        return h->fused_pool && h->win12 && s.name == "conv1_2" && c->cin == 64 && c->cout == 64 && c->ks == 3 &&
+    auto conv12_win_ok = [&](size_t li, const DevConv* c) {
+        return h->fused_pool && h->win12 && li == 1 && vgg[li].pool && c->cin == 64 && c->cout == 64 && c->ks == 3 &&
                c->pad == 1 && c->Mpad == 64 && c->nK6 == 18 && !c->small6;
     };
     auto conv12_win = [&](size_t i, const Spec& s, DevConv* c, int lvl) {
@@ -484,17 +483,15 @@ static void run_trunk_x6(opose_ctx* h, int net, const std::vector<NetSeg>& segs,
         h->prof_end(pe);
         bs[i].cur = out;
     };
-    int lvl = 0;
     for (size_t li = 0; li < vgg.size(); ++li) {
-        const Spec& s = vgg[li];
-        DevConv* c = find_conv(h, net, s.name);
-        if (h->gate_ev && s.name == gate_layer()) {  // OPOSE_PIPELINE_DEFER: the previous post may start
-            OPOSE_HIP_CHECK(hipEventRecord(h->gate_ev, h->stream));
-            h->gate_done = true;
-        }
+        const Spec& s = vgg[li].s;
+        const int lvl = vgg[li].lvl;
+        const bool pooled = vgg[li].pool;
+        DevConv* c = t.trunk[li];
+        if ((int)li == d.gate_trunk) record_gate(h);
         if (li == 0 && s.cin == 3 && s.cout == 64 && s.ks == 3 && s.pad == 1 && vgg.size() > 1 && h->first_direct) {
-            DevConv* c2 = find_conv(h, net, vgg[1].name);
-            const bool pair12 = conv12_win_ok(vgg[1], c2);
+            DevConv* c2 = t.trunk[1];
+            const bool pair12 = conv12_win_ok(1, c2);
             const bool f32 = pair12 && h->c11_f32;
             if (ns > 1 && ns <= (size_t)kConv1Segs && pair12) {
                 // a pyramid's conv1_1 and conv1_2 as one launch each over every segment: the
@@ -526,11 +523,10 @@ static void run_trunk_x6(opose_ctx* h, int net, const std::vector<NetSeg>& segs,
                 launch_conv_first_x6_segs(S1, c->wt, c->Mpad, c->bias, f32, h->stream);
                 h->prof_end(pe);
                 h->prof_begin(pe, "conv3x3", f2, 0);
-                if (h->detail) pe.detail = "layer/" + vgg[1].name + "/x6win/g" + std::to_string(ns) + "/n" + std::to_string(px2);
+                if (h->detail) pe.detail = "layer/" + vgg[1].s.name + "/x6win/g" + std::to_string(ns) + "/n" + std::to_string(px2);
                 launch_conv3_pool_win_x6_segs(S2, c2->wx6, c2->bias, f32, h->stream);
                 h->prof_end(pe);
                 ++li;
-                ++lvl;
                 continue;
             }
             for (size_t i = 0; i < ns; ++i) conv11_direct(i, s, c, f32);
@@ -550,10 +546,8 @@ static void run_trunk_x6(opose_ctx* h, int net, const std::vector<NetSeg>& segs,
         }
         const bool final_layer = li + 1 == vgg.size();
         const int og = (s.cout + 7) / 8;
-        const bool pooled = s.name == "conv1_2" || s.name == "conv2_2" || s.name == "conv3_4";
-        if (pooled && conv12_win_ok(s, c)) {
+        if (conv12_win_ok(li, c)) {
             for (size_t i = 0; i < ns; ++i) conv12_win(i, s, c, lvl);
-            ++lvl;
             continue;
         }
         std::vector<ConvSeg> cs;
@@ -568,11 +562,7 @@ static void run_trunk_x6(opose_ctx* h, int net, const std::vector<NetSeg>& segs,
         }
         run_conv_x6_segs(h, cs, fuse);
         for (size_t i = 0; i < ns; ++i) bs[i].cur = outs[i];
-        if (fuse) {
-            ++lvl;
-            continue;
-        }
-        if (pooled) {  // separate MaxPool2d(2, 2) (fused_pool off: dense buffers throughout)
+        if (pooled && !fuse) {  // separate MaxPool2d(2, 2) (fused_pool off: dense buffers throughout)
             for (size_t i = 0; i < ns; ++i) {
                 const NetSeg& sg = segs[i];
                 const int hh = sg.Hp >> lvl, ww = sg.Wp >> lvl;
@@ -587,30 +577,64 @@ static void run_trunk_x6(opose_ctx* h, int net, const std::vector<NetSeg>& segs,
                 h->prof_end(pe);
                 b.cur = pd;
             }
-            ++lvl;
         }
     }
 }
 
-// output rows of a band's trunk past each cut edge (engine body_net_x6; src/dist.py BAND_MARGIN)
+// ---------------------------------------------------------------- the CPM stages, both paths
+// Where a stage's step reads or writes: the stage-input concat S[k] (whole, its trunk slice, or a
+// branch's output slice), the branches' activations T[k], or stage 1's hidden 1x1 outputs U.
+struct Place {
+    enum Buf { S, T, U } buf;
+    int k;  // which of S[2] / T[2]
+    enum Part { Whole, Trunk, Branch } part;
+};
+
+// The stages of a forward in launch order, once the trunk has written the trunk slice of S[0] and
+// S[1] (src/model.py:106-133, :197-214).  conv(st, c0, c1, in, out): one layer with ReLU; c1 null:
+// c0 on `in` and `out` as they are (a stage's opening layer, every branch's outputs in one conv),
+// else c0 / c1 on branch 0's / 1's slices.  close(st, c, in, mid, out, relu2): per branch b the
+// 1x1 pair c[b][0] -> c[b][1] from in through mid to out, the second with ReLU where relu2[b].
+// Returns k of the S buffer the last stage wrote.
+template <class Conv, class Close>
+static int walk_stages(const NetDesc& d, const NetTable& t, Conv&& conv, Close&& close) {
+    int cur = 0;
+    for (int st = 1; st <= kStages; ++st, cur ^= 1) {
+        const NetTable::Stage& ts = t.stages[st - 1];
+        const Place sin{Place::S, cur, st == 1 ? Place::Trunk : Place::Whole};
+        if (ts.open) conv(st, ts.open, nullptr, sin, Place{Place::T, 0, Place::Whole});
+        int tb = 0;
+        for (size_t m = 0; m < ts.mid[0].size(); ++m, tb ^= 1)
+            conv(st, ts.mid[0][m], d.branches == 2 ? ts.mid[1][m] : nullptr, Place{Place::T, tb, Place::Branch},
+                 Place{Place::T, tb ^ 1, Place::Branch});
+        // stage 1's pair is wider than T: through U
+        close(st, ts.close, ts.open ? Place{Place::T, tb, Place::Branch} : sin,
+              st == 1 ? Place{Place::U, 0, Place::Branch} : Place{Place::T, tb ^ 1, Place::Branch},
+              Place{Place::S, cur ^ 1, Place::Branch}, d.stages[st - 1].relu2);
+    }
+    return cur;
+}
+
+// output rows of a band's trunk past each cut edge (net_forward_x6; src/dist.py BAND_MARGIN)
 constexpr int kBandTrunkMargin = 10;
 
-// bodypose_model.forward on X6 activations, every segment in lockstep; per segment the fp32
-// output in its slot's S0 with the fp32 path's layout (channel stride 185: paf [0,38), heat [38,57)).
-// band: one segment of one frame, stages on rows [band->r0, band->r1) only, output in band->maps.
-std::vector<float*> body_net_x6(opose_ctx* h, const std::vector<NetSeg>& segs, const Band* band) {
-    const int SG = 24, TG = 32, UG = 128;  // [L1 | L2 | trunk] = 5 + 3 + 16 groups; 256 / 1024 channels
-    const int net = OPOSE_NET_BODY;
+// A network's forward on X6 activations, every segment in lockstep; per segment the fp32 output in
+// its slot's S0 with the fp32 path's layout (channel stride NetDesc::Sc, branch b at s_off[b]).
+// band (body only): one segment of one frame, stages on rows [band->r0, band->r1) only, output in
+// band->maps.
+std::vector<float*> net_forward_x6(opose_ctx* h, int net, const std::vector<NetSeg>& segs, const Band* band) {
+    const NetDesc& d = net_desc(net);
+    const NetTable& t = net_table(h, net);
     const size_t ns = segs.size();
     // per segment: S (stage inputs) and T (branch activations): padded X6P, read by the 7x7 / 3x3
-    // convs; U (conv5_4 output, read by the 1x1 conv5_5): dense
+    // convs; U (stage 1's hidden 1x1 outputs, read by its second 1x1): dense
     struct Bufs {
         uint8_t *S[2], *T[2], *U;
-        float* O;
         int N, hl, wl;
     };
     std::vector<Bufs> bs(ns);
     std::vector<XAct> last, dup;
+    std::vector<float*> outs;
     for (size_t i = 0; i < ns; ++i) {
         auto& w = h->ws[segs[i].slot];
         Bufs& b = bs[i];
@@ -618,15 +642,15 @@ std::vector<float*> body_net_x6(opose_ctx* h, const std::vector<NetSeg>& segs, c
         b.hl = segs[i].Hp / 8;
         b.wl = segs[i].Wp / 8;
         const size_t px = (size_t)b.N * b.hl * b.wl, plane = x6p_plane(b.N, b.hl, b.wl);
-        b.S[0] = w.x6S0.ensure<uint8_t>(plane * SG * 48, h->stream);
-        b.S[1] = w.x6S1.ensure<uint8_t>(plane * SG * 48, h->stream);
-        b.T[0] = w.x6T0.ensure<uint8_t>(plane * TG * 48, h->stream);
-        b.T[1] = w.x6T1.ensure<uint8_t>(plane * TG * 48, h->stream);
-        b.U = w.x6U.ensure<uint8_t>(px * UG * 48, h->stream);
-        b.O = w.S0.ensure<float>(px * 185, h->stream);
-        clear_x6p_pads(h, {{&w.x6S0, SG}, {&w.x6S1, SG}, {&w.x6T0, TG}, {&w.x6T1, TG}}, b.N, b.hl, b.wl);
-        last.push_back(x6pact(b.S[0], SG, 8, b.N, b.hl, b.wl));
-        dup.push_back(x6pact(b.S[1], SG, 8, b.N, b.hl, b.wl));
+        b.S[0] = w.x6S0.ensure<uint8_t>(plane * d.SG * 48, h->stream);
+        b.S[1] = w.x6S1.ensure<uint8_t>(plane * d.SG * 48, h->stream);
+        b.T[0] = w.x6T0.ensure<uint8_t>(plane * d.TG * 48, h->stream);
+        b.T[1] = w.x6T1.ensure<uint8_t>(plane * d.TG * 48, h->stream);
+        b.U = w.x6U.ensure<uint8_t>(px * d.UG * 48, h->stream);
+        outs.push_back(w.S0.ensure<float>(px * d.Sc, h->stream));
+        clear_x6p_pads(h, {{&w.x6S0, d.SG}, {&w.x6S1, d.SG}, {&w.x6T0, d.TG}, {&w.x6T1, d.TG}}, b.N, b.hl, b.wl);
+        last.push_back(x6pact(b.S[0], d.SG, d.trunk_goff, b.N, b.hl, b.wl));
+        dup.push_back(x6pact(b.S[1], d.SG, d.trunk_goff, b.N, b.hl, b.wl));
     }
     if (band && (ns != 1 || bs[0].N != 1 || band->r0 < 0 || band->r1 > bs[0].hl || band->r1 - band->r0 < 3))
         throw std::invalid_argument("row band: one frame, 3 <= r1 - r0 rows inside the map");
@@ -642,9 +666,15 @@ std::vector<float*> body_net_x6(opose_ctx* h, const std::vector<NetSeg>& segs, c
         }
         return a;
     };
-    auto s_ = [&](size_t i, int k, int goff) { return bview(x6pact(bs[i].S[k], SG, goff, bs[i].N, bs[i].hl, bs[i].wl)); };
-    auto t_ = [&](size_t i, int k, int goff) { return bview(x6pact(bs[i].T[k], TG, goff, bs[i].N, bs[i].hl, bs[i].wl)); };
-    auto u_ = [&](size_t i, int goff) { return x6act(bs[i].U, UG, goff, bs[i].N, rows(i), bs[i].wl); };
+    // segment i's activation at p, branch b's slice where p names the branches'
+    auto at = [&](size_t i, Place p, int b) {
+        const Bufs& B = bs[i];
+        if (p.buf == Place::S)
+            return bview(x6pact(B.S[p.k], d.SG, p.part == Place::Trunk ? d.trunk_goff : p.part == Place::Branch ? d.s_goff[b] : 0,
+                                B.N, B.hl, B.wl));
+        if (p.buf == Place::T) return bview(x6pact(B.T[p.k], d.TG, p.part == Place::Branch ? b * kMid / 8 : 0, B.N, B.hl, B.wl));
+        return x6act(B.U, d.UG, b * kHidden / 8, B.N, rows(i), B.wl);
+    };
     // band edges: send the band's first / last 3 rows of groups [g0, g0 + ng) of X6P buffer buf
     // (cg groups) up / down, receive the neighbours' rows into the rows above / below the band
     auto band_halo = [&](uint8_t* buf, int cg, int g0, int ng) {
@@ -679,20 +709,6 @@ std::vector<float*> body_net_x6(opose_ctx* h, const std::vector<NetSeg>& segs, c
                         h->stream);
         h->prof_end(pe);
     };
-    // one layer over every segment: branch L1 (conv c1) and, when c2, branch L2
-    auto layer = [&](const std::string& n1, const std::string& n2, const std::function<XAct(size_t)>& in1,
-                     const std::function<XAct(size_t)>& out1, const std::function<XAct(size_t)>& in2,
-                     const std::function<XAct(size_t)>& out2, bool relu1, bool relu2) {
-        DevConv* c1 = find_conv(h, net, n1);
-        DevConv* c2 = n2.empty() ? nullptr : find_conv(h, net, n2);
-        std::vector<ConvSeg> cs;
-        for (size_t i = 0; i < ns; ++i) {
-            cs.push_back(ConvSeg{c1, bs[i].N, rows(i), bs[i].wl, in1(i), out1(i), XAct{}, relu1, bs[i].hl});
-            if (c2) cs.push_back(ConvSeg{c2, bs[i].N, rows(i), bs[i].wl, in2(i), out2(i), XAct{}, relu2, bs[i].hl});
-        }
-        run_conv_x6_segs(h, cs);
-    };
-    auto none = [](size_t) { return XAct{}; };
     if (band) {
         // the band's trunk on the input rows its stages need: out1 rows [r0 - 3, r1 + 3) (the 7x7
         // Mconv1 halo) plus kBandTrunkMargin - 3 rows that a cut edge's zero padding corrupts
@@ -709,221 +725,69 @@ std::vector<float*> body_net_x6(opose_ctx* h, const std::vector<NetSeg>& segs, c
             v.l.fs = (uint32_t)(b - a + 3) * v.l.rs;
             return v;
         };
-        run_trunk_x6(h, net, {NetSeg{xs, 1, Hs, Wp, segs[0].slot, Hp}}, {sub(last[0])}, {sub(dup[0])});
+        run_trunk_x6(h, d, t, {NetSeg{xs, 1, Hs, Wp, segs[0].slot, Hp}}, {sub(last[0])}, {sub(dup[0])});
     } else {
-        run_trunk_x6(h, net, segs, last, dup);
+        run_trunk_x6(h, d, t, segs, last, dup);
     }
-    layer("conv5_1_CPM_L1+L2", "", [&](size_t i) { return s_(i, 0, 8); }, [&](size_t i) { return t_(i, 0, 0); }, none,
-          none, true, false);
-    band_halo(bs[0].T[0], TG, 0, TG);
-    layer("conv5_2_CPM_L1", "conv5_2_CPM_L2", [&](size_t i) { return t_(i, 0, 0); },
-          [&](size_t i) { return t_(i, 1, 0); }, [&](size_t i) { return t_(i, 0, 16); },
-          [&](size_t i) { return t_(i, 1, 16); }, true, true);
-    band_halo(bs[0].T[1], TG, 0, TG);
-    layer("conv5_3_CPM_L1", "conv5_3_CPM_L2", [&](size_t i) { return t_(i, 1, 0); },
-          [&](size_t i) { return t_(i, 0, 0); }, [&](size_t i) { return t_(i, 1, 16); },
-          [&](size_t i) { return t_(i, 0, 16); }, true, true);
-    // 1x1 pairs of both branches and every segment: L1 then L2 of each segment
-    auto chain = [&](const std::string& a1, const std::string& a2, const std::string& b1, const std::string& b2,
-                     const std::function<ChainSeg(size_t, int, DevConv*, DevConv*)>& mk) {
-        DevConv *ca1 = find_conv(h, net, a1), *ca2 = find_conv(h, net, a2);
-        DevConv *cb1 = find_conv(h, net, b1), *cb2 = find_conv(h, net, b2);
-        std::vector<ChainSeg> cs;
-        for (size_t i = 0; i < ns; ++i) {
-            cs.push_back(mk(i, 0, ca1, ca2));
-            cs.push_back(mk(i, 1, cb1, cb2));
-        }
-        run_chain_x6(h, cs);
-    };
-    chain("conv5_4_CPM_L1", "conv5_5_CPM_L1", "conv5_4_CPM_L2", "conv5_5_CPM_L2",
-          [&](size_t i, int br, DevConv* c1, DevConv* c2) {
-              return ChainSeg{c1, c2, bs[i].N, rows(i), bs[i].wl, t_(i, 0, br ? 16 : 0), u_(i, br ? 64 : 0),
-                              s_(i, 1, br ? 5 : 0), false, bs[i].hl};
-          });
-    band_halo(bs[0].S[1], SG, 0, 8);
-    int cur = 1;
-    for (int st = 2; st <= 6; ++st) {
-        const std::string sf = "_stage" + std::to_string(st);
-        if (h->gate_ev && gate_layer() == "stage" + std::to_string(st)) {
-            OPOSE_HIP_CHECK(hipEventRecord(h->gate_ev, h->stream));
-            h->gate_done = true;
-        }
-        layer("Mconv1" + sf + "_L1+L2", "", [&](size_t i) { return s_(i, cur, 0); },
-              [&](size_t i) { return t_(i, 0, 0); }, none, none, true, false);
-        int t = 0;
-        for (int k = 2; k <= 5; ++k) {
-            band_halo(bs[0].T[t], TG, 0, TG);  // Mconv2..5 read 3 rows past the band
-            const std::string nm = "Mconv" + std::to_string(k) + sf;
-            layer(nm + "_L1", nm + "_L2", [&](size_t i) { return t_(i, t, 0); },
-                  [&](size_t i) { return t_(i, t ^ 1, 0); }, [&](size_t i) { return t_(i, t, 16); },
-                  [&](size_t i) { return t_(i, t ^ 1, 16); }, true, true);
-            t ^= 1;
-        }
-        // Mconv6 -> Mconv7; Mconv7: no ReLU, except Mconv7_stage6_L2 (no_relu list quirk,
-        // src/model.py:30-33)
-        chain("Mconv6" + sf + "_L1", "Mconv7" + sf + "_L1", "Mconv6" + sf + "_L2", "Mconv7" + sf + "_L2",
-              [&](size_t i, int br, DevConv* c1, DevConv* c2) {
-                  const XAct o = st < 6 ? s_(i, cur ^ 1, br ? 5 : 0)
-                                 : band ? f32act(band->maps, 57, br ? 38 : 0) : f32act(bs[i].O, 185, br ? 38 : 0);
-                  return ChainSeg{c1, c2, bs[i].N, rows(i), bs[i].wl, t_(i, t, br ? 16 : 0), t_(i, t ^ 1, br ? 16 : 0), o,
-                                  br == 1 && st == 6, bs[i].hl};
-              });
-        if (st < 6) band_halo(bs[0].S[cur ^ 1], SG, 0, 8);  // the next Mconv1 (7x7) reads them
-        cur ^= 1;
-    }
-    std::vector<float*> outs;
-    for (const Bufs& b : bs) outs.push_back(b.O);
-    return outs;
-}
-
-// handpose_model.forward on X6 activations, every segment in lockstep; per segment the fp32
-// output in its slot's S0, channel stride 150 (heat [0,22))
-std::vector<float*> hand_net_x6(opose_ctx* h, const std::vector<NetSeg>& segs) {
-    const int SG = 19, TG = 16, UG = 64;  // [L 22 + 2 | trunk 128] = 3 + 16 groups; 128 / 512 channels
-    const int net = OPOSE_NET_HAND;
-    const size_t ns = segs.size();
-    struct Bufs {
-        uint8_t *S[2], *T[2], *U;
-        float* O;
-        int N, hl, wl;
-    };
-    std::vector<Bufs> bs(ns);
-    std::vector<XAct> last, dup;
-    for (size_t i = 0; i < ns; ++i) {
-        auto& w = h->ws[segs[i].slot];
-        Bufs& b = bs[i];
-        b.N = segs[i].N;
-        b.hl = segs[i].Hp / 8;
-        b.wl = segs[i].Wp / 8;
-        const size_t px = (size_t)b.N * b.hl * b.wl, plane = x6p_plane(b.N, b.hl, b.wl);
-        b.S[0] = w.x6S0.ensure<uint8_t>(plane * SG * 48, h->stream);
-        b.S[1] = w.x6S1.ensure<uint8_t>(plane * SG * 48, h->stream);
-        b.T[0] = w.x6T0.ensure<uint8_t>(plane * TG * 48, h->stream);
-        b.T[1] = w.x6T1.ensure<uint8_t>(plane * TG * 48, h->stream);
-        b.U = w.x6U.ensure<uint8_t>(px * UG * 48, h->stream);
-        b.O = w.S0.ensure<float>(px * 150, h->stream);
-        clear_x6p_pads(h, {{&w.x6S0, SG}, {&w.x6S1, SG}, {&w.x6T0, TG}, {&w.x6T1, TG}}, b.N, b.hl, b.wl);
-        last.push_back(x6pact(b.S[0], SG, 3, b.N, b.hl, b.wl));
-        dup.push_back(x6pact(b.S[1], SG, 3, b.N, b.hl, b.wl));
-    }
-    auto s_ = [&](size_t i, int k, int goff) { return x6pact(bs[i].S[k], SG, goff, bs[i].N, bs[i].hl, bs[i].wl); };
-    auto t_ = [&](size_t i, int k) { return x6pact(bs[i].T[k], TG, 0, bs[i].N, bs[i].hl, bs[i].wl); };
-    auto u_ = [&](size_t i) { return x6act(bs[i].U, UG, 0, bs[i].N, bs[i].hl, bs[i].wl); };
-    auto layer = [&](const std::string& name, const std::function<XAct(size_t)>& in,
-                     const std::function<XAct(size_t)>& out, bool relu) {
-        DevConv* c = find_conv(h, net, name);
-        std::vector<ConvSeg> cs;
-        for (size_t i = 0; i < ns; ++i) cs.push_back(ConvSeg{c, bs[i].N, bs[i].hl, bs[i].wl, in(i), out(i), XAct{}, relu});
-        run_conv_x6_segs(h, cs);
-    };
-    auto chain = [&](const std::string& n1, const std::string& n2, const std::function<ChainSeg(size_t, DevConv*, DevConv*)>& mk) {
-        DevConv *c1 = find_conv(h, net, n1), *c2 = find_conv(h, net, n2);
-        std::vector<ChainSeg> cs;
-        for (size_t i = 0; i < ns; ++i) cs.push_back(mk(i, c1, c2));
-        run_chain_x6(h, cs);
-    };
-    run_trunk_x6(h, net, segs, last, dup);
-    chain("conv6_1_CPM", "conv6_2_CPM", [&](size_t i, DevConv* c1, DevConv* c2) {
-        return ChainSeg{c1, c2, bs[i].N, bs[i].hl, bs[i].wl, s_(i, 0, 3), u_(i), s_(i, 1, 0), false};
-    });
-    int cur = 1;
-    for (int st = 2; st <= 6; ++st) {
-        const std::string sf = "_stage" + std::to_string(st);
-        layer("Mconv1" + sf, [&](size_t i) { return s_(i, cur, 0); }, [&](size_t i) { return t_(i, 0); }, true);
-        int t = 0;
-        for (int k = 2; k <= 5; ++k) {
-            layer("Mconv" + std::to_string(k) + sf, [&](size_t i) { return t_(i, t); },
-                  [&](size_t i) { return t_(i, t ^ 1); }, true);
-            t ^= 1;
-        }
-        chain("Mconv6" + sf, "Mconv7" + sf, [&](size_t i, DevConv* c1, DevConv* c2) {
-            const XAct o = st == 6 ? f32act(bs[i].O, 150, 0) : s_(i, cur ^ 1, 0);
-            return ChainSeg{c1, c2, bs[i].N, bs[i].hl, bs[i].wl, t_(i, t), t_(i, t ^ 1), o, false};
+    walk_stages(
+        d, t,
+        [&](int st, DevConv* c0, DevConv* c1, Place in, Place out) {
+            if (in.buf == Place::S && st == d.gate_stage) record_gate(h);
+            // a 3x3 / 7x7 layer reads 3 rows of T past the band
+            if (in.buf == Place::T && c0->ks > 1) band_halo(bs[0].T[in.k], d.TG, 0, d.TG);
+            std::vector<ConvSeg> cs;
+            for (size_t i = 0; i < ns; ++i) {
+                cs.push_back(ConvSeg{c0, bs[i].N, rows(i), bs[i].wl, at(i, in, 0), at(i, out, 0), XAct{}, true, bs[i].hl});
+                if (c1) cs.push_back(ConvSeg{c1, bs[i].N, rows(i), bs[i].wl, at(i, in, 1), at(i, out, 1), XAct{}, true, bs[i].hl});
+            }
+            run_conv_x6_segs(h, cs);
+        },
+        [&](int st, DevConv* const(*c)[2], Place in, Place mid, Place out, const bool* relu2) {
+            // every segment's branches in one launch; the last stage writes the fp32 output
+            std::vector<ChainSeg> cs;
+            for (size_t i = 0; i < ns; ++i)
+                for (int b = 0; b < d.branches; ++b) {
+                    const XAct o = st < kStages ? at(i, out, b)
+                                   : band       ? f32act(band->maps, d.trunk_off, d.s_off[b])
+                                                : f32act(outs[i], d.Sc, d.s_off[b]);
+                    cs.push_back(ChainSeg{c[b][0], c[b][1], bs[i].N, rows(i), bs[i].wl, at(i, in, b), at(i, mid, b), o,
+                                          relu2[b], bs[i].hl});
+                }
+            run_chain_x6(h, cs);
+            if (st < kStages) band_halo(bs[0].S[out.k], d.SG, 0, d.trunk_goff);  // the next opening 7x7 reads them
         });
-        cur ^= 1;
-    }
-    std::vector<float*> outs;
-    for (const Bufs& b : bs) outs.push_back(b.O);
     return outs;
 }
 
-// bodypose_model.forward (src/model.py:106-133). Output: S-buffer with paf [0,38), heat [38,57)
-float* body_net(opose_ctx* h, const float* x, int N, int Hp, int Wp) {
-    if (!h->loaded[OPOSE_NET_BODY]) throw std::runtime_error("body weights not loaded");
-    if (h->x6) return body_net_x6(h, {NetSeg{x, N, Hp, Wp, h->slot}})[0];
+// A network's forward (src/model.py:106-133, :197-214).  Output: S buffer, channel stride
+// NetDesc::Sc, branch b's maps at s_off[b] (body: paf [0,38), heat [38,57); hand: heat [0,22))
+float* net_forward(opose_ctx* h, int net, const float* x, int N, int Hp, int Wp) {
+    const NetDesc& d = net_desc(net);
+    const NetTable& t = net_table(h, net);
+    if (h->x6) return net_forward_x6(h, net, {NetSeg{x, N, Hp, Wp, h->slot}})[0];
     const int hl = Hp / 8, wl = Wp / 8;
     const size_t px = (size_t)N * hl * wl;
-    float* S[2] = {h->w().S0.ensure<float>(px * 185, h->stream), h->w().S1.ensure<float>(px * 185, h->stream)};
-    float* T[2] = {h->w().T0.ensure<float>(px * 256, h->stream), h->w().T1.ensure<float>(px * 256, h->stream)};
-    float* U = h->w().U.ensure<float>(px * 1024, h->stream);
-    const int net = OPOSE_NET_BODY;
-    run_trunk(h, net, x, N, Hp, Wp, Act{S[0], 185, 57}, Act{S[1], 185, 57});
-    // stage 1 (src/model.py:52-62): input = trunk slice of S0
-    run_conv(h, find_conv(h, net, "conv5_1_CPM_L1+L2"), nullptr, N, hl, wl, Act{S[0], 185, 57}, Act{T[0], 256, 0},
-             Act{}, Act{}, true, false);
-    run_conv(h, find_conv(h, net, "conv5_2_CPM_L1"), find_conv(h, net, "conv5_2_CPM_L2"), N, hl, wl,
-             Act{T[0], 256, 0}, Act{T[1], 256, 0}, Act{T[0], 256, 128}, Act{T[1], 256, 128}, true, true);
-    run_conv(h, find_conv(h, net, "conv5_3_CPM_L1"), find_conv(h, net, "conv5_3_CPM_L2"), N, hl, wl,
-             Act{T[1], 256, 0}, Act{T[0], 256, 0}, Act{T[1], 256, 128}, Act{T[0], 256, 128}, true, true);
-    run_conv(h, find_conv(h, net, "conv5_4_CPM_L1"), find_conv(h, net, "conv5_4_CPM_L2"), N, hl, wl,
-             Act{T[0], 256, 0}, Act{U, 1024, 0}, Act{T[0], 256, 128}, Act{U, 1024, 512}, true, true);
-    run_conv(h, find_conv(h, net, "conv5_5_CPM_L1"), find_conv(h, net, "conv5_5_CPM_L2"), N, hl, wl,
-             Act{U, 1024, 0}, Act{S[1], 185, 0}, Act{U, 1024, 512}, Act{S[1], 185, 38}, false, false);
-    int cur = 1;
-    for (int st = 2; st <= 6; ++st) {
-        const std::string s = "_stage" + std::to_string(st);
-        float* in = S[cur];
-        float* out = S[cur ^ 1];
-        run_conv(h, find_conv(h, net, "Mconv1" + s + "_L1+L2"), nullptr, N, hl, wl, Act{in, 185, 0},
-                 Act{T[0], 256, 0}, Act{}, Act{}, true, false);
-        int t = 0;
-        for (int i = 2; i <= 6; ++i) {
-            const std::string nm = "Mconv" + std::to_string(i) + s;
-            run_conv(h, find_conv(h, net, nm + "_L1"), find_conv(h, net, nm + "_L2"), N, hl, wl, Act{T[t], 256, 0},
-                     Act{T[t ^ 1], 256, 0}, Act{T[t], 256, 128}, Act{T[t ^ 1], 256, 128}, true, true);
-            t ^= 1;
-        }
-        // Mconv7: no ReLU, except Mconv7_stage6_L2 (no_relu list quirk, src/model.py:30-33)
-        run_conv(h, find_conv(h, net, "Mconv7" + s + "_L1"), find_conv(h, net, "Mconv7" + s + "_L2"), N, hl, wl,
-                 Act{T[t], 256, 0}, Act{out, 185, 0}, Act{T[t], 256, 128}, Act{out, 185, 38}, false, st == 6);
-        cur ^= 1;
-    }
-    return S[cur];
-}
-
-// handpose_model.forward (src/model.py:197-214). Output: S-buffer with heat [0,22)
-float* hand_net(opose_ctx* h, const float* x, int N, int Hp, int Wp) {
-    if (!h->loaded[OPOSE_NET_HAND]) throw std::runtime_error("hand weights not loaded");
-    if (h->x6) return hand_net_x6(h, {NetSeg{x, N, Hp, Wp, h->slot}})[0];
-    const int hl = Hp / 8, wl = Wp / 8;
-    const size_t px = (size_t)N * hl * wl;
-    float* S[2] = {h->w().S0.ensure<float>(px * 150, h->stream), h->w().S1.ensure<float>(px * 150, h->stream)};
-    float* T[2] = {h->w().T0.ensure<float>(px * 128, h->stream), h->w().T1.ensure<float>(px * 128, h->stream)};
-    float* U = h->w().U.ensure<float>(px * 512, h->stream);
-    const int net = OPOSE_NET_HAND;
-    run_trunk(h, net, x, N, Hp, Wp, Act{S[0], 150, 22}, Act{S[1], 150, 22});
-    run_conv(h, find_conv(h, net, "conv6_1_CPM"), nullptr, N, hl, wl, Act{S[0], 150, 22}, Act{U, 512, 0}, Act{},
-             Act{}, true, false);
-    run_conv(h, find_conv(h, net, "conv6_2_CPM"), nullptr, N, hl, wl, Act{U, 512, 0}, Act{S[1], 150, 0}, Act{},
-             Act{}, false, false);
-    int cur = 1;
-    for (int st = 2; st <= 6; ++st) {
-        const std::string s = "_stage" + std::to_string(st);
-        float* in = S[cur];
-        float* out = S[cur ^ 1];
-        run_conv(h, find_conv(h, net, "Mconv1" + s), nullptr, N, hl, wl, Act{in, 150, 0}, Act{T[0], 128, 0}, Act{},
-                 Act{}, true, false);
-        int t = 0;
-        for (int i = 2; i <= 6; ++i) {
-            run_conv(h, find_conv(h, net, "Mconv" + std::to_string(i) + s), nullptr, N, hl, wl, Act{T[t], 128, 0},
-                     Act{T[t ^ 1], 128, 0}, Act{}, Act{}, true, false);
-            t ^= 1;
-        }
-        run_conv(h, find_conv(h, net, "Mconv7" + s), nullptr, N, hl, wl, Act{T[t], 128, 0}, Act{out, 150, 0}, Act{},
-                 Act{}, false, false);
-        cur ^= 1;
-    }
-    return S[cur];
+    float* S[2] = {h->w().S0.ensure<float>(px * d.Sc, h->stream), h->w().S1.ensure<float>(px * d.Sc, h->stream)};
+    float* T[2] = {h->w().T0.ensure<float>(px * d.Tc, h->stream), h->w().T1.ensure<float>(px * d.Tc, h->stream)};
+    float* U = h->w().U.ensure<float>(px * d.Uc, h->stream);
+    auto at = [&](Place p, int b) {
+        if (p.buf == Place::S)
+            return Act{S[p.k], d.Sc, p.part == Place::Trunk ? d.trunk_off : p.part == Place::Branch ? d.s_off[b] : 0};
+        if (p.buf == Place::T) return Act{T[p.k], d.Tc, p.part == Place::Branch ? b * kMid : 0};
+        return Act{U, d.Uc, b * kHidden};
+    };
+    // a layer's conv, or both branches' convs in one launch (c1 null: one conv)
+    auto pair = [&](DevConv* c0, DevConv* c1, Place in, Place out, bool relu0, bool relu1) {
+        run_conv(h, c0, c1, N, hl, wl, at(in, 0), at(out, 0), c1 ? at(in, 1) : Act{}, c1 ? at(out, 1) : Act{}, relu0, relu1);
+    };
+    run_trunk(h, d, t, x, N, Hp, Wp, at(Place{Place::S, 0, Place::Trunk}, 0), at(Place{Place::S, 1, Place::Trunk}, 0));
+    const int k = walk_stages(
+        d, t, [&](int, DevConv* c0, DevConv* c1, Place in, Place out) { pair(c0, c1, in, out, true, true); },
+        [&](int, DevConv* const(*c)[2], Place in, Place mid, Place out, const bool* relu2) {
+            pair(c[0][0], c[1][0], in, mid, true, true);  // (one branch: c[1] is null)
+            pair(c[0][1], c[1][1], mid, out, relu2[0], relu2[1]);
+        });
+    return S[k];
 }
 
 }  // namespace opose

@@ -13,7 +13,9 @@ Cases: every row of test_gpu_x6.CASES with both epilogues (fp32 NCHW and the X6 
 three WINO_CASES rows on the window kernel (mt = -2) and on Winograd (mt = -3), and four whole
 networks: the body at (2, 3, 72, 104) by default, with OPOSE_WINO=1 and with OPOSE_CONV7_WIN=0,
 and the hand pyramid (48, 96, 144) of one crop -- the chain kernel, the pooled epilogues,
-conv1_1 / conv1_2 and the slab fixup."""
+conv1_1 / conv1_2 and the slab fixup.  The fp32 MFMA forwards (OPOSE_CONV=f32; conv.hip has no
+atomics, its stream-K fixup folds in a fixed order) are pinned too: the body at the same shape
+and the hand network at (2, 3, 40, 24)."""
 import hashlib
 import json
 import os
@@ -41,6 +43,7 @@ CONV_ROWS = [  # test_gpu_x6.CASES
 WINO_ROWS = [(2, 128, 23, 41, 256), (3, 40, 11, 13, 128), (2, 128, 9, 7, 96)]  # of test_gpu_x6.WINO_CASES
 BODY_SHAPE = (2, 3, 72, 104)
 HAND_SIZES = (48, 96, 144)
+HAND_F32_SHAPE = (2, 3, 40, 24)  # two frames, a 5 x 3 output map: conv.hip's stream-K fixup runs
 
 
 def _conv_inputs(N, Cin, H, W, Cout, ks, seed):
@@ -78,6 +81,15 @@ def _hand(native, handle):
     return xs + list(seeded_state_dict("hand", 0).values()), lambda: list(_hand_model({}).forward_pyramid(xs))
 
 
+def _hand_f32(native, handle):
+    from src.model import handpose_model
+    from src.weights import seeded_state_dict
+    from test_gpu_x6 import _model_outputs
+    x = np.random.default_rng(12).random(HAND_F32_SHAPE, dtype=np.float32) - np.float32(0.5)
+    env = {"OPOSE_CONV": "f32"}
+    return [x] + list(seeded_state_dict("hand", 0).values()), lambda: list(_model_outputs(handpose_model, "hand", x, env))
+
+
 def _cases():
     """id -> f(native, handle) -> (input arrays, thunk giving the output arrays)"""
     out = {}
@@ -97,6 +109,8 @@ def _cases():
     out["net-body-wino"] = _body({"OPOSE_WINO": "1"})
     out["net-body-no-conv7-win"] = _body({"OPOSE_CONV7_WIN": "0"})
     out["net-hand-pyramid"] = _hand
+    out["net-body-f32"] = _body({"OPOSE_CONV": "f32"})
+    out["net-hand-f32"] = _hand_f32
     return out
 
 
