@@ -382,6 +382,26 @@ int opose_debug_heat(opose_t* h, const float* maps, int hl, int wl, int pad_down
  * map over the component (elsewhere undefined) */
 int opose_debug_hand_label(opose_t* h, const double* maps, int NP, int H, int W, double thre, int32_t* labels,
                            double* sums);
+/* The fast mode's stages (srcmx/Batch_model.py), each through the launchers the product path uses.
+ * srcmx/Batch_model.py:147-150 for N uint8 BGR frames (strides in bytes) at `boxsize` and the one
+ * scale `scale`: out [N,3,Hp,Wp]; HpWp receives (Hp, Wp) (out may be NULL to query the size) */
+int opose_debug_batch_preprocess(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                                 int64_t frame_stride, double boxsize, double scale, float* out, int* HpWp);
+/* srcmx/Batch_model.py:159-168: maps [N,57,hl,wl] (PAF 0..37, heat 38..56) -> heat [N,18,H,W]
+ * float32, the map the blur and the peak search read, and (optional) mid [N,56,nh,nw], the x8
+ * maps cropped to nh x nw */
+int opose_debug_batch_heat(opose_t* h, const float* maps, int N, int hl, int wl, int nh, int nw, int H, int W,
+                           float* heat, float* mid);
+/* srcmx/utilmx.py:230-263 on NP float32 maps [NP,H,W]: 5x5 blur, then peaks > thre that are >=
+ * their 4 neighbours -> cnt [NP] (every peak), list [NP,cap] (y * W + x of the first cap peaks,
+ * in no order; unused slots -1) and score [NP,cap] (the blurred values) */
+int opose_debug_blur5_nms(opose_t* h, const float* heat, int NP, int H, int W, double thre, int cap, int32_t* cnt,
+                          int32_t* list, double* score);
+/* srcmx/Batch_model.py:334-346 on NP float32 maps [NP,H,W]: blurred [NP,H,W] float64 (float32
+ * values), binary = blurred > thre, labels and sums as opose_debug_hand_label's (sums over the
+ * blurred map) */
+int opose_debug_batch_hand_label(opose_t* h, const float* heat, int NP, int H, int W, double thre, double* blurred,
+                                 int32_t* labels, double* sums);
 
 #ifdef __cplusplus
 }

@@ -37,23 +37,26 @@ def size_pad(g_scale, h, w, boxsize=368, stride=8):
     return scale, nh, nw, (stride - nh % stride) % stride, (stride - nw % stride) % stride
 
 
-def to_tensor(frames_u8: np.ndarray) -> torch.Tensor:
-    """transforms.ToTensor() on each uint8 BGR HWC frame, stacked: [B, 3, h, w] float32."""
-    return torch.from_numpy(np.ascontiguousarray(frames_u8.transpose(0, 3, 1, 2))).float().div(255)
+def to_tensor(frames_u8: np.ndarray, dtype=torch.float32) -> torch.Tensor:
+    """transforms.ToTensor() on each uint8 BGR HWC frame, stacked: [B, 3, h, w] (float32 there)."""
+    return torch.from_numpy(np.ascontiguousarray(frames_u8.transpose(0, 3, 1, 2))).to(dtype).div(255)
 
 
-def net_input(frames_u8: np.ndarray, g_scale=0.5, boxsize=368, stride=8):
-    x = to_tensor(frames_u8)
+def net_input(frames_u8: np.ndarray, g_scale=0.5, boxsize=368, stride=8, dtype=torch.float32):
+    """dtype: the arithmetic of the division, the resize and the subtraction.  float32 is the
+    reference's own; float64 is the high-precision statement of the same operation."""
+    x = to_tensor(frames_u8, dtype)
     _, _, h, w = x.shape
     scale, nh, nw, ph, pw = size_pad(g_scale, h, w, boxsize, stride)
     x = F.interpolate(x, scale_factor=scale, mode="bicubic") - 0.5
     return F.pad(x, [0, pw, 0, ph], mode="constant", value=0), (h, w, nh, nw)
 
 
-def blur5(heat: torch.Tensor) -> torch.Tensor:
+def blur5(heat: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """dtype: the arithmetic of the sums; the weights are the reference's float32 values in both."""
     c = heat.shape[1]
-    k = torch.tensor(GAUSS5, dtype=torch.float32)[None, None].expand(c, 1, 5, 5)
-    return F.conv2d(F.pad(heat, (2, 2, 2, 2), mode="reflect"), k, groups=c)
+    k = torch.tensor(GAUSS5, dtype=torch.float32).to(dtype)[None, None].expand(c, 1, 5, 5)
+    return F.conv2d(F.pad(heat.to(dtype), (2, 2, 2, 2), mode="reflect"), k, groups=c)
 
 
 def find_peaks(data: torch.Tensor, thre: float) -> torch.Tensor:
@@ -65,14 +68,19 @@ def find_peaks(data: torch.Tensor, thre: float) -> torch.Tensor:
     return torch.nonzero(b, as_tuple=False)
 
 
-def post(paf_low: torch.Tensor, heat_low: torch.Tensor, geo, thre1=0.1, thre2=0.05, stride=8):
+def resize_chain(low: torch.Tensor, geo, stride=8, dtype=torch.float32):
+    """The two resizes of `post` in dtype arithmetic: (x8 map cropped to nh x nw, map at h x w)."""
+    h, w, nh, nw = geo
+    mid = F.interpolate(low.to(dtype), scale_factor=stride, mode="bicubic")[:, :, :nh, :nw]
+    return mid, F.interpolate(mid, size=(h, w), mode="bicubic")
+
+
+def post(paf_low: torch.Tensor, heat_low: torch.Tensor, geo, thre1=0.1, thre2=0.05, stride=8, dtype=torch.float32):
     """Everything after the network for a batch: list of (candidate, subset)."""
     h, w, nh, nw = geo
-    heat = F.interpolate(heat_low, scale_factor=stride, mode="bicubic")[:, :, :nh, :nw]
-    heat = F.interpolate(heat, size=(h, w), mode="bicubic")
-    paf = F.interpolate(paf_low, scale_factor=stride, mode="bicubic")[:, :, :nh, :nw]
-    paf = F.interpolate(paf, size=(h, w), mode="bicubic").numpy().transpose(0, 2, 3, 1)
-    heat = blur5(heat)
+    heat = resize_chain(heat_low, geo, stride, dtype)[1]
+    paf = resize_chain(paf_low, geo, stride, dtype)[1].numpy().transpose(0, 2, 3, 1)
+    heat = blur5(heat, dtype)
     peaks = find_peaks(heat[:, :-1], thre1).numpy()
     heat = heat.numpy().transpose(0, 2, 3, 1)
     B = heat.shape[0]
@@ -96,11 +104,11 @@ def batch_body_infer(frames_u8: np.ndarray, net_fn, g_scale=0.5, thre1=0.1, thre
     return post(torch.from_numpy(np.asarray(paf)), torch.from_numpy(np.asarray(heat)), geo, thre1, thre2)
 
 
-def hand_post(heat_low: torch.Tensor, thre=0.035, stride=8):
+def hand_post(heat_low: torch.Tensor, thre=0.035, stride=8, dtype=torch.float32):
     """Batch_hand.__call__ after the network (srcmx/Batch_model.py:334-354) -> np.array [B, 21, 3]."""
     from .hand_post import label8, npmax
-    heat = F.interpolate(heat_low, scale_factor=stride, mode="bicubic")
-    heat = blur5(heat).numpy().transpose(0, 2, 3, 1)
+    heat = F.interpolate(heat_low.to(dtype), scale_factor=stride, mode="bicubic")
+    heat = blur5(heat, dtype).numpy().transpose(0, 2, 3, 1)
     out = []
     for i in range(heat.shape[0]):
         peaks = []

@@ -153,6 +153,13 @@ struct ScaleGeom {
     double up_sy, up_sx;  // final resize (Hs,Ws) -> (H,W) source steps
 };
 
+// geometry of a fast-mode frame (engine_api.cpp batch_geom)
+struct BatchGeom {
+    double scale;  // boxsize * scale_search / H
+    int nh, nw;    // int(H * scale), int(W * scale)
+    int Hp, Wp;    // padded to stride
+};
+
 struct GraphEntry {
     hipGraphExec_t exec = nullptr;
     uint64_t epoch = 0;
@@ -290,6 +297,8 @@ ScaleGeom geom(double s, const opose_params& p, int H, int W);
 ScaleGeom geom_from_pads(int hl, int wl, int pad_down, int pad_right, int H, int W);
 void body_post_common(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, const opose_params& p,
                       uint8_t* rec_dev);
+void batch_resize_chain(opose_ctx* h, int N, int H, int W, const float* maps, int cstride, int hl, int wl, int nh,
+                        int nw, float* mid, float* heat);
 void batch_post_common(opose_ctx* h, int N, int H, int W, const float* maps, int cstride, int hl, int wl, int nh,
                        int nw, const opose_params& p, uint8_t* rec_dev);
 void hand_post_common(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, const opose_params& p,
@@ -304,8 +313,13 @@ int finish_records(opose_ctx* h, int N, void* records, uint8_t* rec_dev, int fla
 // engine_api.cpp
 void flush_post(opose_ctx* h);
 void enter_main(opose_ctx* h);
+const uint8_t* stage_frames(opose_ctx* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                            int64_t frame_stride, int flags);
 void preprocess_scale(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
                       const ScaleGeom& g, const opose_params& p, float* x, hipStream_t stream);
+BatchGeom batch_geom(const opose_params& p, int H, int W);
+void batch_preprocess(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
+                      const BatchGeom& g, float* x, hipStream_t stream);
 // engine_rccl.cpp
 const Rccl& rccl();
 void rccl_check(ncclResult_t r);

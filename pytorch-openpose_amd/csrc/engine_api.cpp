@@ -12,7 +12,7 @@ static size_t host_span(int N, int H, int W, int64_t row_stride, int64_t frame_s
 
 // a strided uint8 [N][H][W][3] view of the frames on the device: the caller's pointer
 // (OPOSE_IN_DEVICE), or the copy of the host frames in h->frames
-static const uint8_t* stage_frames(opose_ctx* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+const uint8_t* stage_frames(opose_ctx* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
                                    int64_t frame_stride, int flags) {
     if (flags & OPOSE_IN_DEVICE) return bgr;
     uint8_t* buf = h->frames.ensure<uint8_t>((size_t)frame_stride * N, h->stream);
@@ -36,6 +36,25 @@ void preprocess_scale(const uint8_t* frames, int64_t frame_stride, int64_t row_s
                       const ScaleGeom& g, const opose_params& p, float* x, hipStream_t stream) {
     launch_preprocess(frames, frame_stride, row_stride, N, H, W, g.Hs, g.Ws, 1.0 / g.mult, 1.0 / g.mult, g.Hp, g.Wp,
                       (float)p.pad_value / 256.f - 0.5f, x, stream);
+}
+
+// Batch_body.calculate_size_pad (srcmx/Batch_model.py:302-307): int() truncation
+BatchGeom batch_geom(const opose_params& p, int H, int W) {
+    BatchGeom g;
+    g.scale = p.boxsize * p.scales[0] / H;
+    g.nh = (int)(H * g.scale);
+    g.nw = (int)(W * g.scale);
+    if (g.nh <= 0 || g.nw <= 0) throw std::invalid_argument("scale produces an empty image");
+    g.Hp = round_up(g.nh, p.stride);
+    g.Wp = round_up(g.nw, p.stride);
+    return g;
+}
+
+// the fast mode's network input x [N][3][Hp][Wp] of N frames (srcmx/Batch_model.py:147-150)
+void batch_preprocess(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
+                      const BatchGeom& g, float* x, hipStream_t stream) {
+    const float sc = (float)(1.0 / g.scale);  // torch: float(1 / scale_factor)
+    launch_preprocess_torch(frames, frame_stride, row_stride, N, H, W, g.nh, g.nw, sc, sc, g.Hp, g.Wp, x, stream);
 }
 
 static opose_params fill_params(const opose_params* p, int net) {
@@ -545,11 +564,8 @@ int opose_body_post_scales(opose_t* h, const float* const* maps, const int* hl, 
 template <class F>
 static uint8_t* run_batch_body(opose_ctx* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
                                int64_t frame_stride, const opose_params& p, int flags, F&& rec_of) {
-    // Batch_body.calculate_size_pad (srcmx/Batch_model.py:302-307): int() truncation
-    const double scale = p.boxsize * p.scales[0] / H;
-    const int nh = (int)(H * scale), nw = (int)(W * scale);
-    if (nh <= 0 || nw <= 0) throw std::invalid_argument("scale produces an empty image");
-    const int Hp = round_up(nh, p.stride), Wp = round_up(nw, p.stride);
+    const BatchGeom g = batch_geom(p, H, W);
+    const int nh = g.nh, nw = g.nw, Hp = g.Hp, Wp = g.Wp;
     const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, flags);
     uint8_t* rec = rec_of();
     const std::string key = call_key("batch_body", N, H, W, row_stride, frame_stride, p, fd, rec, h->ppp, h->maxp);
@@ -557,8 +573,7 @@ static uint8_t* run_batch_body(opose_ctx* h, const uint8_t* bgr, int N, int H, i
         float* x = h->w().x.ensure<float>((size_t)N * 3 * Hp * Wp, h->stream);
         ProfEntry pe;
         h->prof_begin(pe, "preprocess", 0, (double)N * (3.0 * H * W + 12.0 * Hp * Wp));
-        const float sc = (float)(1.0 / scale);  // torch: float(1 / scale_factor)
-        launch_preprocess_torch(fd, frame_stride, row_stride, N, H, W, nh, nw, sc, sc, Hp, Wp, x, h->stream);
+        batch_preprocess(fd, frame_stride, row_stride, N, H, W, g, x, h->stream);
         h->prof_end(pe);
         float* S = net_forward(h, OPOSE_NET_BODY, x, N, Hp, Wp);
         batch_post_common(h, N, H, W, S, 185, Hp / 8, Wp / 8, nh, nw, p, rec);

@@ -335,3 +335,99 @@ int opose_debug_hand_label(opose_t* h, const double* maps, int NP, int H, int W,
     return OPOSE_OK;
 }
 
+int opose_debug_batch_preprocess(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                                 int64_t frame_stride, double boxsize, double scale, float* out, int* HpWp) {
+    if (!h || !bgr || !HpWp || N <= 0 || H <= 0 || W <= 0 || boxsize <= 0 || scale <= 0) return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        opose_params p;
+        opose_default_params(OPOSE_NET_BODY, &p);
+        p.boxsize = boxsize;
+        p.n_scales = 1;
+        p.scales[0] = scale;
+        const BatchGeom g = batch_geom(p, H, W);
+        HpWp[0] = g.Hp;
+        HpWp[1] = g.Wp;
+        if (!out) return OPOSE_OK;
+        DevBuf xo;
+        const size_t nx = (size_t)N * 3 * g.Hp * g.Wp;
+        const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, 0);
+        float* xd = xo.ensure<float>(nx, h->stream);
+        batch_preprocess(fd, frame_stride, row_stride, N, H, W, g, xd, h->stream);
+        OPOSE_HIP_CHECK(hipMemcpyAsync(out, xd, nx * 4, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    });
+    return OPOSE_OK;
+}
+
+int opose_debug_batch_heat(opose_t* h, const float* maps, int N, int hl, int wl, int nh, int nw, int H, int W,
+                           float* heat, float* mid) {
+    if (!h || !maps || !heat || N <= 0 || hl <= 0 || wl <= 0 || H <= 0 || W <= 0) return OPOSE_E_ARG;
+    if (nh <= 0 || nw <= 0 || nh > 8 * hl || nw > 8 * wl) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        DevBuf min_, mb, hb;
+        const size_t nm = (size_t)N * 57 * hl * wl, nmid = (size_t)N * 56 * nh * nw, nheat = (size_t)N * 18 * H * W;
+        float* md = min_.ensure<float>(nm, h->stream);
+        float* midd = mb.ensure<float>(nmid, h->stream);
+        float* hd = hb.ensure<float>(nheat, h->stream);
+        OPOSE_HIP_CHECK(hipMemcpyAsync(md, maps, nm * 4, hipMemcpyHostToDevice, h->stream));
+        batch_resize_chain(h, N, H, W, md, 57, hl, wl, nh, nw, midd, hd);
+        OPOSE_HIP_CHECK(hipMemcpyAsync(heat, hd, nheat * 4, hipMemcpyDeviceToHost, h->stream));
+        if (mid) OPOSE_HIP_CHECK(hipMemcpyAsync(mid, midd, nmid * 4, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_debug_blur5_nms(opose_t* h, const float* heat, int NP, int H, int W, double thre, int cap, int32_t* cnt,
+                          int32_t* list, double* score) {
+    if (!h || !heat || !cnt || !list || !score || NP <= 0 || H <= 0 || W <= 0 || cap <= 0) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        DevBuf hb, cb, lb, sb;
+        const size_t n = (size_t)NP * H * W, nl = (size_t)NP * cap;
+        float* hd = hb.ensure<float>(n, h->stream);
+        int* cd = cb.ensure<int>((size_t)NP, h->stream);
+        int* ld = lb.ensure<int>(nl, h->stream);
+        double* sd = sb.ensure<double>(nl, h->stream);
+        OPOSE_HIP_CHECK(hipMemcpyAsync(hd, heat, n * 4, hipMemcpyHostToDevice, h->stream));
+        OPOSE_HIP_CHECK(hipMemsetAsync(cd, 0, sizeof(int) * NP, h->stream));
+        OPOSE_HIP_CHECK(hipMemsetAsync(ld, 0xff, sizeof(int) * nl, h->stream));  // unused slots: -1
+        OPOSE_HIP_CHECK(hipMemsetAsync(sd, 0, sizeof(double) * nl, h->stream));
+        launch_blur5_nms(hd, NP, H, W, thre, cap, cd, ld, sd, h->stream);
+        OPOSE_HIP_CHECK(hipMemcpyAsync(cnt, cd, sizeof(int) * NP, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(list, ld, sizeof(int) * nl, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(score, sd, sizeof(double) * nl, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    });
+    return OPOSE_OK;
+}
+
+int opose_debug_batch_hand_label(opose_t* h, const float* heat, int NP, int H, int W, double thre, double* blurred,
+                                 int32_t* labels, double* sums) {
+    if (!h || !heat || !blurred || !labels || !sums || NP <= 0 || H <= 0 || W <= 0) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const size_t n = (size_t)NP * H * W;
+        DevBuf hb, bb, lb, sb, cb, pk, fd, ws;
+        float* hd = hb.ensure<float>(n, h->stream);
+        double* bd = bb.ensure<double>(n, h->stream);
+        int* lab = lb.ensure<int>(n, h->stream);
+        double* sd = sb.ensure<double>(n, h->stream);
+        int* cnt = cb.ensure<int>((size_t)NP, h->stream);
+        OPOSE_HIP_CHECK(hipMemcpyAsync(hd, heat, n * 4, hipMemcpyHostToDevice, h->stream));
+        OPOSE_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * NP, h->stream));
+        launch_blur5_seed(hd, NP, H, W, thre, bd, lab, cnt, h->stream);
+        launch_hand_cc(bd, NP, H, W, lab, sd, cnt, pk.ensure<double>((size_t)NP * 3, h->stream),
+                       fd.ensure<int>((size_t)NP, h->stream), ws.ensure<uint8_t>(hand_cc_workspace_bytes(NP), h->stream),
+                       false, h->stream);
+        OPOSE_HIP_CHECK(hipMemcpyAsync(blurred, bd, n * 8, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(labels, lab, n * 4, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(sums, sd, n * 8, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    });
+    return OPOSE_OK;
+}

@@ -189,17 +189,25 @@ void body_to_mid(opose_ctx* h, int s, const float* maps, int cstride, int N, con
 // cropped to nh x nw, torch bicubic to H x W, 5x5 blur + peaks on the blurred map, then the
 // shared limb scoring / greedy matching / assembly.  maps: [N][cstride][hl][wl] with PAF
 // channels 0..37 and heat 38..56.
+// batch_resize_chain: the two resizes, into mid [N][56][nh][nw] (PAF and heat x8, cropped) and
+// heat [N][18][H][W].
+void batch_resize_chain(opose_ctx* h, int N, int H, int W, const float* maps, int cstride, int hl, int wl, int nh,
+                        int nw, float* mid, float* heat) {
+    ProfEntry pe;
+    h->prof_begin(pe, "upsample8", 0, (double)N * 56 * nh * nw * 4);
+    launch_upsample8_torch(maps, cstride, 0, 56, N, hl, wl, nh, nw, mid, h->stream);
+    h->prof_end(pe);
+    h->prof_begin(pe, "heat_full", 0, (double)N * 18 * (4.0 * H * W + 4.0 * nh * nw));
+    launch_resize_torch_f32(mid, 56, 38, 18, N, nh, nw, H, W, heat, h->stream);
+    h->prof_end(pe);
+}
+
 void batch_post_common(opose_ctx* h, int N, int H, int W, const float* maps, int cstride, int hl, int wl, int nh,
                        int nw, const opose_params& p, uint8_t* rec_dev) {
     ProfEntry pe;
     float* mid = h->mid(0).ensure<float>((size_t)N * 56 * nh * nw, h->stream);
-    h->prof_begin(pe, "upsample8", 0, (double)N * 56 * nh * nw * 4);
-    launch_upsample8_torch(maps, cstride, 0, 56, N, hl, wl, nh, nw, mid, h->stream);
-    h->prof_end(pe);
     float* heat = reinterpret_cast<float*>(h->avg.ensure<double>((size_t)N * 18 * H * W, h->stream));
-    h->prof_begin(pe, "heat_full", 0, (double)N * 18 * (4.0 * H * W + 4.0 * nh * nw));
-    launch_resize_torch_f32(mid, 56, 38, 18, N, nh, nw, H, W, heat, h->stream);
-    h->prof_end(pe);
+    batch_resize_chain(h, N, H, W, maps, cstride, hl, wl, nh, nw, mid, heat);
     PafScales S{};
     S.mid[0] = mid;
     S.hs[0] = nh;

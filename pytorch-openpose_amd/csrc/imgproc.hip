@@ -354,12 +354,35 @@ void launch_upsample8_torch(const float* in, int in_cstride, int in_coff, int C,
     launch_resize_rows<0>(st, in, in_cstride, in_coff, C, N, hl, wl, nh, nw, 0.125, 0.125, 1.f, 0, (void*)out, 1);
 }
 
-// torch bicubic to H x W (size given: scale = float(nh) / float(H)); float map out
+// torch bicubic resize of mid [N][Cm][nh][nw] channels [coff, coff+P) to [H][W], a thread per
+// pixel: cubic_resize_rows<1>'s values (the same expressions in the same order) where a
+// workgroup's source rows do not fit the staged rows, as heat_full_accum is for the OpenCV taps
+__global__ __launch_bounds__(256) void resize_torch_pixel(const float* __restrict__ mid, int Cm, int coff, int P,
+                                                          int nh, int nw, int H, int W, float scale_y,
+                                                          float scale_x, float* __restrict__ out) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    const int np = blockIdx.z;
+    if (x >= W) return;
+    const int n = np / P, p = np - n * P;
+    const CubicTap ty = cubic_tap_torch(y, scale_y, nh);
+    const CubicTap tx = cubic_tap_torch(x, scale_x, nw);
+    const float* plane = mid + ((size_t)n * Cm + coff + p) * nh * nw;
+    out[((size_t)np * H + y) * W + x] = 0.f + cubic_sample_f32(plane, nw, ty, tx);
+}
+
+// torch bicubic to H x W (size given: scale = float(nh) / float(H)); float map out.  The
+// row-staged resize where its rows fit (nh / H <= 2.4375), else a thread per pixel: frames
+// shorter than boxsize * scale / 2.4375 rows (76 at the defaults) take the second
 void launch_resize_torch_f32(const float* mid, int Cm, int coff, int P, int N, int nh, int nw, int H, int W,
                              float* out, hipStream_t st) {
     const float sy = (float)nh / (float)H, sx = (float)nw / (float)W;
-    if (!rows_fit(sy)) throw std::invalid_argument("fast mode: downscale too strong for the staged resize");
-    launch_resize_rows<1>(st, mid, Cm, coff, P, N, nh, nw, H, W, (double)sy, (double)sx, 1.f, 0, (void*)out, 1);
+    if (rows_fit(sy)) {
+        launch_resize_rows<1>(st, mid, Cm, coff, P, N, nh, nw, H, W, (double)sy, (double)sx, 1.f, 0, (void*)out, 1);
+        return;
+    }
+    dim3 grid((W + 255) / 256, H, N * P);
+    hipLaunchKernelGGL(resize_torch_pixel, grid, dim3(256), 0, st, mid, Cm, coff, P, nh, nw, H, W, sy, sx, out);
 }
 
 }  // namespace opose

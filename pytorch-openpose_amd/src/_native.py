@@ -86,6 +86,10 @@ SIGNATURES = {
     "opose_debug_conv_x6_time": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "opose_debug_heat": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "opose_debug_hand_label": (_I, [_P, _P, _I, _I, _I, _D, _P, _P]),
+    "opose_debug_batch_preprocess": (_I, [_P, _P, _I, _I, _I, _L, _L, _D, _D, _P, _P]),
+    "opose_debug_batch_heat": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "opose_debug_blur5_nms": (_I, [_P, _P, _I, _I, _I, _D, _I, _P, _P, _P]),
+    "opose_debug_batch_hand_label": (_I, [_P, _P, _I, _I, _I, _D, _P, _P, _P]),
 }
 EXPORTED = list(SIGNATURES)
 
