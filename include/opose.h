@@ -365,6 +365,43 @@ int opose_debug_conv_time(opose_t* h, int N, int Cin, int H, int W, int Cout, in
 int opose_debug_conv_x6(opose_t* h, const float* x, const float* w, const float* b, int N, int Cin, int H,
                         int W, int Cout, int ks, int pad, int relu, int mt, int pt, int splits, int out_x6,
                         float* out);
+/* Layer-level hooks of the network kernels (tests/test_gpu_conv_layers.py), each through the
+ * launch path the forward uses; the host splits fp32 inputs into X6 and joins X6 outputs.
+ *
+ * One conv launch sequence (run_conv_x6_segs) over nseg = 1 .. 8 segments of one conv shape
+ * (Cin, Cout, ks, pad ks / 2).  geom [nseg][6] per segment: N, H, W, forced k slabs (0: the
+ * planner's count), weight set (< nw <= 2) and the output offset (first channel of the fp32 buffer
+ * or first group of the X6 buffer).  x[i] [N,Cin,H,W]; w[k] [Cout,Cin,ks,ks], b[k] [Cout].
+ * family: -1 the planner's choice, else 0 conv_x6, 1 the window kernel, 2 the window kernel per
+ * frame, 3 Winograd (OPOSE_E_ARG when the shape does not fit the forced family).  pool: the fused
+ * 2x2 max-pool (outputs H/2 x W/2).  in_padded: the input as X6P, else dense X6.  out_kind 0: fp32
+ * NCHW buffers of out_total channels; 1 / 2: dense X6 / X6P buffers of out_total groups.  dup:
+ * also a duplicate destination of the output's kind (X6 kinds only).  net, lvl, pair: the layer's
+ * network, resolution level and CPM-pair flag as the slab policy sees them.
+ * out[i] (and out_dup[i]) [N,Cout,Ho,Wo]; ran [nseg][2]: the family the planner names for the
+ * segment and the k slabs it ran with; clobbered: 16-byte units (fp32 buffers: elements) outside
+ * the written pixels' slice of any output allocation that the launch changed (every allocation is
+ * filled with a byte pattern first; the pad channels of the last written group do not count). */
+int opose_debug_conv_segs(opose_t* h, int nseg, const int* geom, const float* const* x, int nw,
+                          const float* const* w, const float* const* b, int Cin, int Cout, int ks, int relu,
+                          int family, int pool, int in_padded, int out_kind, int out_total, int dup, int net,
+                          int lvl, int pair, float* const* out, float* const* out_dup, int* ran,
+                          int64_t* clobbered);
+/* The fused closing 1x1 pair (conv1x1_chain_x6) on nseg = 1 or 2 segments of 128-channel inputs
+ * (geom [nseg][4]: N, H, W, weight set < nw <= 2): out[i] [N,cout2,H,W] = W2 relu(W1 x + b1) + b2
+ * (+ ReLU when relu2), W1 [m1,128] with m1 = 128 or 512, W2 [cout2,m1] with cout2 <= 64; the input
+ * as X6P (in_padded) or dense X6, the output as fp32 or (out_x6) an X6P slice. */
+int opose_debug_chain(opose_t* h, int nseg, const int* geom, const float* const* x, int nw,
+                      const float* const* w1, const float* const* b1, const float* const* w2,
+                      const float* const* b2, int m1, int cout2, int relu2, int in_padded, int out_x6,
+                      float* const* out);
+/* The first two layers' own kernels on nseg = 1 .. 8 segments (geom [nseg][3]: N, H, W) in one
+ * launch, bias and ReLU applied as in the networks.  stage 1: conv1_1 (conv_first_x6), x[i]
+ * [N,3,H,W], w [64,3,3,3] -> out[i] [N,64,H,W]; f32: the kernel's fp32-unit output form, else X6.
+ * stage 2: conv1_2 + MaxPool2d(2, 2) (conv3_pool_win_x6), x[i] [N,64,H,W], w [64,64,3,3] -> out[i]
+ * [N,64,H/2,W/2]; f32: the kernel's fp32-unit input form, else X6. */
+int opose_debug_conv1(opose_t* h, int stage, int nseg, const int* geom, const float* const* x, const float* w,
+                      const float* b, int f32, float* const* out);
 int opose_debug_conv_x6_time(opose_t* h, int N, int Cin, int H, int W, int Cout, int ks, int ngroups,
                              int mt, int pt, int splits, int reps, float* ms);
 /* src/body.py:38-41 for one frame and one scale: out [3,Hp,Wp]; HpWp receives (Hp, Wp)

@@ -290,6 +290,7 @@ XAct x6act(uint8_t* p, int cg, int goff, int N, int H, int W);
 size_t x6p_plane(int N, int H, int W);
 XAct x6pact(uint8_t* p, int cg, int goff, int N, int H, int W);
 void run_conv_x6_segs(opose_ctx* h, const std::vector<ConvSeg>& segs, bool pool = false);
+void launch_chain_segs(opose_ctx* h, const std::vector<ChainSeg>& segs);
 std::vector<float*> net_forward_x6(opose_ctx* h, int net, const std::vector<NetSeg>& segs, const Band* band = nullptr);
 float* net_forward(opose_ctx* h, int net, const float* x, int N, int Hp, int Wp);
 // engine_post.cpp

@@ -61,6 +61,53 @@ static TileChoice debug_x6_plan(opose_ctx* h, X6Args& a, int mt, int pt, int sla
     return t;
 }
 
+// ---- the host's X6 split and join (the kernels' split3: each piece the round-to-nearest-even bf16
+// of what the pieces before it left), for activations of any X6Layout (dense or X6P, a group slice)
+static uint16_t bf16_rne(float v) {
+    uint32_t u;
+    std::memcpy(&u, &v, 4);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+static float bf16_f32(uint16_t hb) {
+    const uint32_t u = (uint32_t)hb << 16;
+    float v;
+    std::memcpy(&v, &u, 4);
+    return v;
+}
+static size_t host_unit(const XAct& a, int n, int g, int y, int x) {
+    return (size_t)a.l.o0 + (size_t)n * a.l.fs + (size_t)g * a.l.gs + (size_t)y * a.l.rs + x;
+}
+// x fp32 [N][C][H][W] -> the pixels' units of activation `a` in hx (three piece planes of a.ps bytes)
+static void host_split_x6(const float* x, int N, int C, int H, int W, const XAct& a, uint16_t* hx) {
+    const size_t pl = a.ps / 2;  // bf16 per piece
+    for (int n = 0; n < N; ++n)
+        for (int ch = 0; ch < C; ++ch)
+            for (int y = 0; y < H; ++y)
+                for (int xx = 0; xx < W; ++xx) {
+                    const float v = x[(((size_t)n * C + ch) * H + y) * W + xx];
+                    const size_t e = host_unit(a, n, ch / 8, y, xx) * 8 + ch % 8;
+                    const uint16_t h0 = bf16_rne(v);
+                    const float r = v - bf16_f32(h0);
+                    const uint16_t h1 = bf16_rne(r);
+                    hx[e] = h0;
+                    hx[pl + e] = h1;
+                    hx[2 * pl + e] = bf16_rne(r - bf16_f32(h1));
+                }
+}
+// the piece planes hy of activation `a` -> out fp32 [N][C][H][W] ((x0 + x1) + x2, as from_x6 sums)
+static void host_join_x6(const uint16_t* hy, const XAct& a, int N, int C, int H, int W, float* out) {
+    const size_t pl = a.ps / 2;
+    for (int n = 0; n < N; ++n)
+        for (int ch = 0; ch < C; ++ch)
+            for (int y = 0; y < H; ++y)
+                for (int xx = 0; xx < W; ++xx) {
+                    const size_t e = host_unit(a, n, ch / 8, y, xx) * 8 + ch % 8;
+                    out[(((size_t)n * C + ch) * H + y) * W + xx] =
+                        (bf16_f32(hy[e]) + bf16_f32(hy[pl + e])) + bf16_f32(hy[2 * pl + e]);
+                }
+}
+
 // split-bf16 conv of one layer: x fp32 NCHW -> X6 -> conv_x6 -> fp32 (out_x6: through an X6
 // output buffer and back, exercising the split epilogue)
 int opose_debug_conv_x6(opose_t* h, const float* x, const float* w, const float* b, int N, int Cin, int H, int W,
@@ -76,58 +123,23 @@ int opose_debug_conv_x6(opose_t* h, const float* x, const float* w, const float*
         if (mt <= -2) {
             // padded (X6P) input and output through run_conv_x6_segs with the family under test
             // forced: -2 the window kernel, -3 Winograd (conv_wino_x6); the host splits and joins
-            const size_t plane = x6p_plane(N, H, W), P = (size_t)x6p_pitch(W);
-            auto rne = [](float v) -> uint16_t {
-                uint32_t u;
-                std::memcpy(&u, &v, 4);
-                u += 0x7fffu + ((u >> 16) & 1u);
-                return (uint16_t)(u >> 16);
-            };
-            auto f16 = [](uint16_t hb) {
-                const uint32_t u = (uint32_t)hb << 16;
-                float v;
-                std::memcpy(&v, &u, 4);
-                return v;
-            };
-            std::vector<uint16_t> hx((size_t)3 * cg * plane * 8, 0);
-            const size_t ipl = (size_t)cg * plane * 8;  // bf16 per piece
-            for (int n = 0; n < N; ++n)
-                for (int ch = 0; ch < Cin; ++ch)
-                    for (int y = 0; y < H; ++y)
-                        for (int xx0 = 0; xx0 < W; ++xx0) {
-                            const float v = x[(((size_t)n * Cin + ch) * H + y) * W + xx0];
-                            const size_t u = (size_t)(ch / 8) * plane + (3 + (size_t)n * (H + 3) + y) * P + 3 + xx0;
-                            const uint16_t h0 = rne(v);
-                            const float r = v - f16(h0);
-                            const uint16_t h1 = rne(r);
-                            const uint16_t h2 = rne(r - f16(h1));
-                            hx[u * 8 + ch % 8] = h0;
-                            hx[ipl + u * 8 + ch % 8] = h1;
-                            hx[2 * ipl + u * 8 + ch % 8] = h2;
-                        }
+            XAct ia = x6pact(nullptr, cg, 0, N, H, W), oa = x6pact(nullptr, og, 0, N, H, W);
+            std::vector<uint16_t> hx((size_t)3 * (ia.ps / 2), 0), hy((size_t)3 * (oa.ps / 2));
+            host_split_x6(x, N, Cin, H, W, ia, hx.data());
             DevBuf bi, bo;
-            uint8_t* xi = bi.ensure<uint8_t>(hx.size() * 2, h->stream);
-            const size_t opl = (size_t)og * plane * 8;
-            uint8_t* yo = bo.ensure<uint8_t>(3 * opl * 2, h->stream);
-            OPOSE_HIP_CHECK(hipMemcpyAsync(xi, hx.data(), hx.size() * 2, hipMemcpyHostToDevice, h->stream));
-            OPOSE_HIP_CHECK(hipMemsetAsync(yo, 0, 3 * opl * 2, h->stream));
-            ConvSeg sg{c, N, H, W, x6pact(xi, cg, 0, N, H, W), x6pact(yo, og, 0, N, H, W), XAct{}, relu != 0};
+            ia.p = bi.ensure<uint8_t>(hx.size() * 2, h->stream);
+            oa.p = bo.ensure<uint8_t>(hy.size() * 2, h->stream);
+            OPOSE_HIP_CHECK(hipMemcpyAsync(ia.p, hx.data(), hx.size() * 2, hipMemcpyHostToDevice, h->stream));
+            OPOSE_HIP_CHECK(hipMemsetAsync(oa.p, 0, hy.size() * 2, h->stream));
+            ConvSeg sg{c, N, H, W, ia, oa, XAct{}, relu != 0};
             if (mt == -3) sg.slabs = 1;
             {
                 Redirect<int> family(h->force_kernel, mt == -3 ? kKernelWino : kKernelWin);
                 run_conv_x6_segs(h, {sg});
             }
-            std::vector<uint16_t> hy(3 * opl);
-            OPOSE_HIP_CHECK(hipMemcpyAsync(hy.data(), yo, hy.size() * 2, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(hy.data(), oa.p, hy.size() * 2, hipMemcpyDeviceToHost, h->stream));
             OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
-            for (int n = 0; n < N; ++n)
-                for (int ch = 0; ch < Cout; ++ch)
-                    for (int y = 0; y < H; ++y)
-                        for (int xx0 = 0; xx0 < W; ++xx0) {
-                            const size_t u = (size_t)(ch / 8) * plane + (3 + (size_t)n * (H + 3) + y) * P + 3 + xx0;
-                            out[(((size_t)n * Cout + ch) * H + y) * W + xx0] =
-                                (f16(hy[u * 8 + ch % 8]) + f16(hy[opl + u * 8 + ch % 8])) + f16(hy[2 * opl + u * 8 + ch % 8]);
-                        }
+            host_join_x6(hy.data(), oa, N, Cout, H, W, out);
             h->convs[0].erase("__debug__");
             return OPOSE_OK;
         }
@@ -156,6 +168,344 @@ int opose_debug_conv_x6(opose_t* h, const float* x, const float* w, const float*
         OPOSE_HIP_CHECK(hipMemcpyAsync(out, yd, ny * 4, hipMemcpyDeviceToHost, h->stream));
         OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
         h->convs[0].erase("__debug__");
+    });
+    return OPOSE_OK;
+}
+
+// the hooks' layers, gone from the handle when the hook returns or throws
+struct DebugConvs {
+    opose_ctx* h;
+    int net;
+    std::vector<std::string> keys;
+    DevConv* add(const std::string& key, const Spec& s, const float* w, const float* b, int lvl, bool pair) {
+        upload_conv(h, net, key, {&s}, {w}, {b}, lvl, pair);
+        keys.push_back(key);
+        return h->convs[net][key].get();
+    }
+    ~DebugConvs() {
+        for (const std::string& k : keys) h->convs[net].erase(k);
+    }
+};
+
+constexpr int kDebugFill = 0xa5;  // every byte of an output allocation before the launch under test
+
+// 16-byte units of the piece planes hy of an X6 activation `a` (all_groups groups allocated, og of
+// them written from a's first) that no longer hold the fill pattern although no pixel of the
+// N x H x W frames' slice lives there: pads, other groups
+static int64_t clobbered_units(const uint16_t* hy, const XAct& a, int og, int N, int H, int W) {
+    const size_t units = a.ps / 16;
+    std::vector<uint8_t> written(units, 0);
+    for (int n = 0; n < N; ++n)
+        for (int g = 0; g < og; ++g)
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x) written[host_unit(a, n, g, y, x)] = 1;
+    uint8_t fill[16];
+    std::memset(fill, kDebugFill, 16);
+    int64_t bad = 0;
+    for (int pc = 0; pc < 3; ++pc)
+        for (size_t u = 0; u < units; ++u)
+            if (!written[u] && std::memcmp(hy + ((size_t)pc * units + u) * 8, fill, 16) != 0) ++bad;
+    return bad;
+}
+
+// One run_conv_x6_segs call on 1 .. kX6Groups segments of one conv shape, each with its own frames
+// (geom [nseg][6]: N, H, W, forced k slabs (0: the planner's), weight set, and where its output
+// goes: the first channel of an fp32 buffer or the first group of an X6 buffer).
+int opose_debug_conv_segs(opose_t* h, int nseg, const int* geom, const float* const* x, int nw, const float* const* w,
+                          const float* const* b, int Cin, int Cout, int ks, int relu, int family, int pool,
+                          int in_padded, int out_kind, int out_total, int dup, int net, int lvl, int pair,
+                          float* const* out, float* const* out_dup, int* ran, int64_t* clobbered) {
+    if (!h || !geom || !x || !w || !b || !out || !ran || !clobbered) return OPOSE_E_ARG;
+    if (nseg < 1 || nseg > kX6Groups || nw < 1 || nw > 2 || Cin < 1 || Cout < 1) return OPOSE_E_ARG;
+    if ((ks != 1 && ks != 3 && ks != 7) || family < -1 || family > kKernelWino || out_kind < 0 || out_kind > 2)
+        return OPOSE_E_ARG;
+    if ((net != OPOSE_NET_BODY && net != OPOSE_NET_HAND) || lvl < 0 || lvl > 3) return OPOSE_E_ARG;
+    if (dup && (out_kind == 0 || pool || !out_dup)) return OPOSE_E_ARG;  // (the fp32 epilogue writes no duplicate)
+    if (pool && out_kind == 0) return OPOSE_E_ARG;
+    const int og = (Cout + 7) / 8;
+    for (int i = 0; i < nseg; ++i) {
+        const int* g = geom + 6 * i;
+        if (!x[i] || !out[i] || (dup && !out_dup[i]) || g[0] < 1 || g[1] < 1 || g[2] < 1 || g[3] < 0) return OPOSE_E_ARG;
+        if (g[4] < 0 || g[4] >= nw || !w[g[4]] || !b[g[4]]) return OPOSE_E_ARG;
+        if (g[5] < 0 || g[5] + (out_kind == 0 ? Cout : og) > out_total) return OPOSE_E_ARG;
+        if (pool && (g[1] < 2 || g[2] < 2)) return OPOSE_E_ARG;
+    }
+    OPOSE_TRY(h, {
+        enter_main(h);
+        Spec s{"debug", Cin, Cout, ks, ks / 2};
+        DebugConvs convs{h, net, {}};
+        DevConv* cs[2] = {nullptr, nullptr};
+        for (int k = 0; k < nw; ++k) cs[k] = convs.add("__debug" + std::to_string(k) + "__", s, w[k], b[k], lvl, pair != 0);
+        const int cg = cs[0]->cin_g;
+        // a forced family runs only shapes its launcher takes
+        for (int i = 0; i < nseg; ++i) {
+            const int* g = geom + 6 * i;
+            const bool win = family == kKernelWin || family == kKernelWinFrames;
+            if (win && (!cs[0]->wx6p || !in_padded || pool || !conv_win_fits(family == kKernelWin ? g[0] : 1, g[1], g[2], ks)))
+                return OPOSE_E_ARG;
+            if (family == kKernelWino && (!cs[0]->wwino || !in_padded || pool || g[3] > 1 || wino_tpf(g[0], g[1], g[2]) < 0))
+                return OPOSE_E_ARG;
+        }
+        struct SegBufs {
+            DevBuf in, out, dup;
+            XAct oa, da;
+            size_t obytes = 0;
+            int Ho = 0, Wo = 0;
+        };
+        std::vector<SegBufs> bs(nseg);
+        std::vector<ConvSeg> segs;
+        std::vector<uint16_t> hx;
+        for (int i = 0; i < nseg; ++i) {
+            const int* g = geom + 6 * i;
+            const int N = g[0], H = g[1], W = g[2];
+            SegBufs& B = bs[i];
+            B.Ho = pool ? H / 2 : H;
+            B.Wo = pool ? W / 2 : W;
+            XAct ia = in_padded ? x6pact(nullptr, cg, 0, N, H, W) : x6act(nullptr, cg, 0, N, H, W);
+            hx.assign((size_t)3 * (ia.ps / 2), 0);  // input pads are zero, as in the product
+            host_split_x6(x[i], N, Cin, H, W, ia, hx.data());
+            ia.p = B.in.ensure<uint8_t>(hx.size() * 2, h->stream);
+            OPOSE_HIP_CHECK(hipMemcpyAsync(ia.p, hx.data(), hx.size() * 2, hipMemcpyHostToDevice, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));  // (hx is reused)
+            auto xout = [&](DevBuf& buf) {
+                XAct a = out_kind == 2 ? x6pact(nullptr, out_total, g[5], N, B.Ho, B.Wo)
+                                       : x6act(nullptr, out_total, g[5], N, B.Ho, B.Wo);
+                a.p = buf.ensure<uint8_t>((size_t)3 * a.ps, h->stream);
+                OPOSE_HIP_CHECK(hipMemsetAsync(a.p, kDebugFill, (size_t)3 * a.ps, h->stream));
+                return a;
+            };
+            if (out_kind == 0) {
+                B.obytes = (size_t)N * out_total * H * W * 4;
+                B.oa = XAct{};
+                B.oa.p = B.out.ensure<uint8_t>(B.obytes, h->stream);
+                B.oa.c = out_total;
+                B.oa.off = g[5];
+                B.oa.f32 = true;
+                OPOSE_HIP_CHECK(hipMemsetAsync(B.oa.p, kDebugFill, B.obytes, h->stream));
+            } else {
+                B.oa = xout(B.out);
+                B.obytes = (size_t)3 * B.oa.ps;
+            }
+            if (dup) B.da = xout(B.dup);
+            ConvSeg sg{cs[g[4]], N, H, W, ia, B.oa, dup ? B.da : XAct{}, relu != 0};
+            sg.slabs = g[3];
+            segs.push_back(sg);
+        }
+        {
+            Redirect<int> forced(h->force_kernel, family);  // (-1: the planner's choice)
+            // What run_conv_x6_segs makes of each segment.  The launch leaves no record of it, so this
+            // repeats the first lines of that function's loop (seg_kernel, then a forced count or
+            // slab_count on the segment's N, H, W; the hook's segments carry no Hl): keep the two alike.
+            // A forced count comes back as given -- that it ran shows in the sums (one-hot sets with
+            // a term in each slab, the fixup mutation), not here.
+            for (int i = 0; i < nseg; ++i) {
+                const ConvSeg& sg = segs[i];
+                const int kind = seg_kernel(h, sg, pool != 0);
+                ran[2 * i] = kind;
+                ran[2 * i + 1] = kind == kKernelWino ? 1
+                                 : sg.slabs        ? sg.slabs
+                                                   : slab_count(h, sg.c, kind != kKernelX6, sg.N, sg.H, sg.W, pool != 0);
+            }
+            run_conv_x6_segs(h, segs, pool != 0);
+        }
+        int64_t bad = 0;
+        std::vector<uint8_t> hy;
+        for (int i = 0; i < nseg; ++i) {
+            const int* g = geom + 6 * i;
+            const int N = g[0];
+            SegBufs& B = bs[i];
+            hy.resize(B.obytes);
+            OPOSE_HIP_CHECK(hipMemcpyAsync(hy.data(), B.oa.p, B.obytes, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+            if (out_kind == 0) {
+                const size_t HW = (size_t)B.Ho * B.Wo;
+                const float* y = reinterpret_cast<const float*>(hy.data());
+                float fill;
+                std::memset(&fill, kDebugFill, 4);
+                for (int n = 0; n < N; ++n)
+                    for (int ch = 0; ch < out_total; ++ch) {
+                        const float* src = y + ((size_t)n * out_total + ch) * HW;
+                        if (ch >= g[5] && ch < g[5] + Cout)
+                            std::memcpy(out[i] + ((size_t)n * Cout + ch - g[5]) * HW, src, HW * 4);
+                        else
+                            for (size_t p = 0; p < HW; ++p) bad += std::memcmp(src + p, &fill, 4) != 0;
+                    }
+                continue;
+            }
+            const uint16_t* y = reinterpret_cast<const uint16_t*>(hy.data());
+            host_join_x6(y, B.oa, N, Cout, B.Ho, B.Wo, out[i]);
+            bad += clobbered_units(y, B.oa, og, N, B.Ho, B.Wo);
+            if (dup) {
+                OPOSE_HIP_CHECK(hipMemcpyAsync(hy.data(), B.da.p, B.obytes, hipMemcpyDeviceToHost, h->stream));
+                OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+                host_join_x6(y, B.da, N, Cout, B.Ho, B.Wo, out_dup[i]);
+                bad += clobbered_units(y, B.da, og, N, B.Ho, B.Wo);
+            }
+        }
+        *clobbered = bad;
+    });
+    return OPOSE_OK;
+}
+
+// conv1x1_chain_x6 on one or two segments (geom [nseg][4]: N, H, W, weight set) of 128-channel
+// inputs: Y = W2 relu(W1 X + b1) + b2, W1 [m1][128], W2 [cout2][m1]
+int opose_debug_chain(opose_t* h, int nseg, const int* geom, const float* const* x, int nw, const float* const* w1,
+                      const float* const* b1, const float* const* w2, const float* const* b2, int m1, int cout2,
+                      int relu2, int in_padded, int out_x6, float* const* out) {
+    if (!h || !geom || !x || !w1 || !b1 || !w2 || !b2 || !out) return OPOSE_E_ARG;
+    if (nseg < 1 || nseg > 2 || nw < 1 || nw > 2 || (m1 != 128 && m1 != 512) || cout2 < 1 || cout2 > 64) return OPOSE_E_ARG;
+    for (int i = 0; i < nseg; ++i) {
+        const int* g = geom + 4 * i;
+        if (!x[i] || !out[i] || g[0] < 1 || g[1] < 1 || g[2] < 1 || g[3] < 0 || g[3] >= nw) return OPOSE_E_ARG;
+        if (!w1[g[3]] || !b1[g[3]] || !w2[g[3]] || !b2[g[3]]) return OPOSE_E_ARG;
+    }
+    OPOSE_TRY(h, {
+        enter_main(h);
+        constexpr int Cin = 128;
+        Spec s1{"debug1", Cin, m1, 1, 0}, s2{"debug2", m1, cout2, 1, 0};
+        DebugConvs convs{h, 0, {}};
+        DevConv *c1[2] = {}, *c2[2] = {};
+        for (int k = 0; k < nw; ++k) {
+            c1[k] = convs.add("__debug1_" + std::to_string(k) + "__", s1, w1[k], b1[k], 3, nseg == 2);
+            c2[k] = convs.add("__debug2_" + std::to_string(k) + "__", s2, w2[k], b2[k], 3, nseg == 2);
+            // (what run_chain_x6 asks of a pair before it fuses it)
+            if (c1[k]->cin_g != 16 || c1[k]->cout != c1[k]->Mpad || c2[k]->Mpad != 64 || c2[k]->nK6 != m1 / 32 || c1[k]->small6)
+                return OPOSE_E_ARG;
+        }
+        const int og = (cout2 + 7) / 8;
+        struct SegBufs {
+            DevBuf in, out;
+            XAct oa;
+            size_t obytes = 0;
+        };
+        std::vector<SegBufs> bs(nseg);
+        std::vector<ChainSeg> segs;
+        std::vector<uint16_t> hx;
+        for (int i = 0; i < nseg; ++i) {
+            const int* g = geom + 4 * i;
+            const int N = g[0], H = g[1], W = g[2];
+            SegBufs& B = bs[i];
+            XAct ia = in_padded ? x6pact(nullptr, 16, 0, N, H, W) : x6act(nullptr, 16, 0, N, H, W);
+            hx.assign((size_t)3 * (ia.ps / 2), 0);
+            host_split_x6(x[i], N, Cin, H, W, ia, hx.data());
+            ia.p = B.in.ensure<uint8_t>(hx.size() * 2, h->stream);
+            OPOSE_HIP_CHECK(hipMemcpyAsync(ia.p, hx.data(), hx.size() * 2, hipMemcpyHostToDevice, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+            if (out_x6) {
+                B.oa = x6pact(nullptr, og, 0, N, H, W);
+                B.obytes = (size_t)3 * B.oa.ps;
+            } else {
+                B.oa = XAct{};
+                B.oa.c = cout2;
+                B.oa.f32 = true;
+                B.obytes = (size_t)N * cout2 * H * W * 4;
+            }
+            B.oa.p = B.out.ensure<uint8_t>(B.obytes, h->stream);
+            OPOSE_HIP_CHECK(hipMemsetAsync(B.oa.p, 0, B.obytes, h->stream));
+            segs.push_back(ChainSeg{c1[g[3]], c2[g[3]], N, H, W, ia, XAct{}, B.oa, relu2 != 0});
+        }
+        launch_chain_segs(h, segs);
+        std::vector<uint8_t> hy;
+        for (int i = 0; i < nseg; ++i) {
+            const int* g = geom + 4 * i;
+            SegBufs& B = bs[i];
+            hy.resize(B.obytes);
+            void* dst = out_x6 ? static_cast<void*>(hy.data()) : static_cast<void*>(out[i]);
+            OPOSE_HIP_CHECK(hipMemcpyAsync(dst, B.oa.p, B.obytes, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+            if (out_x6) host_join_x6(reinterpret_cast<const uint16_t*>(hy.data()), B.oa, g[0], cout2, g[1], g[2], out[i]);
+        }
+    });
+    return OPOSE_OK;
+}
+
+// The first two layers' own kernels on 1 .. kConv1Segs segments (geom [nseg][3]: N, H, W) in one
+// launch.  stage 1: conv1_1 (conv_first_x6; x [N,3,H,W], w [64,3,3,3]) -> out [N,64,H,W], f32: its
+// output as fp32 units, else X6.  stage 2: conv1_2 + pool (conv3_pool_win_x6; x [N,64,H,W],
+// w [64,64,3,3]) -> out [N,64,H/2,W/2], f32: its input as fp32 units, else X6.  Both add the bias
+// and apply ReLU, as in the networks.
+int opose_debug_conv1(opose_t* h, int stage, int nseg, const int* geom, const float* const* x, const float* w,
+                      const float* b, int f32, float* const* out) {
+    if (!h || !geom || !x || !w || !b || !out || (stage != 1 && stage != 2) || nseg < 1 || nseg > kConv1Segs)
+        return OPOSE_E_ARG;
+    for (int i = 0; i < nseg; ++i) {
+        const int* g = geom + 3 * i;
+        if (!x[i] || !out[i] || g[0] < 1 || g[1] < stage || g[2] < stage) return OPOSE_E_ARG;
+    }
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const int Cin = stage == 1 ? 3 : 64;
+        Spec s{"debug", Cin, 64, 3, 1};
+        DebugConvs convs{h, 0, {}};
+        DevConv* c = convs.add("__debug__", s, w, b, 0, false);
+        // (what run_trunk_x6 asks of conv1_2 before it runs the window kernel)
+        if (stage == 2 && (c->Mpad != 64 || c->nK6 != 18 || c->small6)) return OPOSE_E_ARG;
+        struct SegBufs {
+            DevBuf in, out;
+            XAct oa;
+            size_t obytes = 0;
+        };
+        std::vector<SegBufs> bs(nseg);
+        Conv1Segs S{};
+        S.n = nseg;
+        std::vector<uint16_t> hx;
+        std::vector<float> hf;
+        for (int i = 0; i < nseg; ++i) {
+            const int* g = geom + 3 * i;
+            const int N = g[0], H = g[1], W = g[2], HW = H * W;
+            const int Ho = stage == 1 ? H : H / 2, Wo = stage == 1 ? W : W / 2;
+            SegBufs& B = bs[i];
+            const void* in;
+            uint32_t ips = 0;
+            if (stage == 1) {
+                float* xd = B.in.ensure<float>((size_t)N * 3 * HW, h->stream);
+                OPOSE_HIP_CHECK(hipMemcpyAsync(xd, x[i], (size_t)N * 3 * HW * 4, hipMemcpyHostToDevice, h->stream));
+                in = xd;
+            } else if (f32) {  // fp32 units [N][8][H*W] of 8 channels
+                hf.resize((size_t)N * 64 * HW);
+                for (int n = 0; n < N; ++n)
+                    for (int ch = 0; ch < 64; ++ch)
+                        for (int p = 0; p < HW; ++p)
+                            hf[(((size_t)n * 8 + ch / 8) * HW + p) * 8 + ch % 8] = x[i][((size_t)n * 64 + ch) * HW + p];
+                float* xd = B.in.ensure<float>(hf.size(), h->stream);
+                OPOSE_HIP_CHECK(hipMemcpyAsync(xd, hf.data(), hf.size() * 4, hipMemcpyHostToDevice, h->stream));
+                in = xd;
+            } else {
+                XAct ia = x6act(nullptr, 8, 0, N, H, W);
+                hx.assign((size_t)3 * (ia.ps / 2), 0);
+                host_split_x6(x[i], N, 64, H, W, ia, hx.data());
+                uint8_t* xd = B.in.ensure<uint8_t>(hx.size() * 2, h->stream);
+                OPOSE_HIP_CHECK(hipMemcpyAsync(xd, hx.data(), hx.size() * 2, hipMemcpyHostToDevice, h->stream));
+                in = xd;
+                ips = ia.ps;
+            }
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));  // (hx / hf are reused)
+            B.oa = x6act(nullptr, 8, 0, N, Ho, Wo);
+            B.obytes = stage == 1 && f32 ? (size_t)N * 64 * HW * 4 : (size_t)3 * B.oa.ps;
+            B.oa.p = B.out.ensure<uint8_t>(B.obytes, h->stream);
+            OPOSE_HIP_CHECK(hipMemsetAsync(B.oa.p, 0, B.obytes, h->stream));
+            S.s[i] = Conv1Seg{in, static_cast<uint8_t*>(B.oa.p), ips, B.oa.ps, N, H, W, 0};
+        }
+        if (stage == 1) launch_conv_first_x6_segs(S, c->wt, c->Mpad, c->bias, f32 != 0, h->stream);
+        else launch_conv3_pool_win_x6_segs(S, c->wx6, c->bias, f32 != 0, h->stream);
+        std::vector<uint8_t> hy;
+        for (int i = 0; i < nseg; ++i) {
+            const int* g = geom + 3 * i;
+            const int N = g[0], Ho = stage == 1 ? g[1] : g[1] / 2, Wo = stage == 1 ? g[2] : g[2] / 2, HWo = Ho * Wo;
+            SegBufs& B = bs[i];
+            hy.resize(B.obytes);
+            OPOSE_HIP_CHECK(hipMemcpyAsync(hy.data(), B.oa.p, B.obytes, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+            if (stage == 1 && f32) {
+                const float* y = reinterpret_cast<const float*>(hy.data());
+                for (int n = 0; n < N; ++n)
+                    for (int ch = 0; ch < 64; ++ch)
+                        for (int p = 0; p < HWo; ++p)
+                            out[i][((size_t)n * 64 + ch) * HWo + p] = y[(((size_t)n * 8 + ch / 8) * HWo + p) * 8 + ch % 8];
+            } else {
+                host_join_x6(reinterpret_cast<const uint16_t*>(hy.data()), B.oa, N, 64, Ho, Wo, out[i]);
+            }
+        }
     });
     return OPOSE_OK;
 }

@@ -319,6 +319,11 @@ static void run_chain_x6(opose_ctx* h, const std::vector<ChainSeg>& segs) {
         run_conv_x6_segs(h, second);
         return;
     }
+    launch_chain_segs(h, segs);
+}
+
+// The fused form: one conv1x1_chain_x6 launch over segments whose pairs run_chain_x6 found to fit it
+void launch_chain_segs(opose_ctx* h, const std::vector<ChainSeg>& segs) {
     X6ChainArgs a{};
     a.cin_g = segs[0].c1->cin_g;
     a.m1 = segs[0].c1->cout;

@@ -83,6 +83,10 @@ SIGNATURES = {
     "opose_debug_preprocess": (_I, [_P, _P, _I, _I, _D, _I, _P, _P]),
     "opose_debug_conv_time": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "opose_debug_conv_x6": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "opose_debug_conv_segs": (_I, [_P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P,
+                                   _P]),
+    "opose_debug_chain": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "opose_debug_conv1": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _P]),
     "opose_debug_conv_x6_time": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "opose_debug_heat": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "opose_debug_hand_label": (_I, [_P, _P, _I, _I, _I, _D, _P, _P]),

@@ -54,9 +54,10 @@ def test_null_handle_is_an_argument_error_everywhere():
         rc = fn(*[t() for t in fn.argtypes])  # a default-constructed ctypes value is 0 / NULL
         assert rc == _native.OPOSE_E_ARG, (name, rc)
         checked.append(name)
-    assert len(checked) >= 47, checked
+    assert len(checked) >= 50, checked
     assert {"opose_debug_batch_preprocess", "opose_debug_batch_heat", "opose_debug_blur5_nms",
-            "opose_debug_batch_hand_label"} <= set(checked)
+            "opose_debug_batch_hand_label", "opose_debug_conv_segs", "opose_debug_chain",
+            "opose_debug_conv1"} <= set(checked)
 
 
 def test_default_params_are_reference_constants():
