@@ -439,6 +439,39 @@ int opose_debug_blur5_nms(opose_t* h, const float* heat, int NP, int H, int W, d
  * blurred map) */
 int opose_debug_batch_hand_label(opose_t* h, const float* heat, int NP, int H, int W, double thre, double* blurred,
                                  int32_t* labels, double* sums);
+/* The body matching kernels (src/body.py:88-208, shared by Body and Batch_body), each through the
+ * launcher the product path uses, at the handle's capacity (opose_set_capacity: cap peaks per part,
+ * max_people rows, the record layout of opose_body_record_bytes).  Whatever a kernel indexes with
+ * is checked first (OPOSE_E_ARG): counts in [0, cap], positions in [0, H * W), connection indices
+ * below their part's count.
+ *
+ * src/body.py:88-94 (np.nonzero's row-major order, the running ids): cnt [N,18] (may pass cap: the
+ * capacity status), list / score [N,18,cap] (y * W + x and the map value of the first cap peaks of
+ * each part, in any order) -> the N records' header and candidate rows, peak_pos [N,18,cap] (the
+ * positions in row-major order, unused slots -1) and part_cnt [N,18] (the clamped counts) */
+int opose_debug_peaks_finalize(opose_t* h, const int32_t* cnt, const int32_t* list, const double* score, int N,
+                               int H, int W, void* records, int32_t* peak_pos, int32_t* part_cnt);
+/* src/body.py:105-141, the score of every (i, j) pair of every limb: score [N,19,cap,cap] holds
+ * limb k's nA x nB scores compactly (pair (i, j) at i * nB + j of the cap * cap block), -inf where
+ * criterion1 / criterion2 fail; every other entry keeps the fill, all bits set (a NaN).  The PAF
+ * maps as the product path makes them, from maps[s] [N,57,hl[s],wl[s]]: fast 0: n_scales scales
+ * with ga / gb = pad_down / pad_right through body_to_mid (src/body.py:52-68); fast 1: one scale
+ * with ga / gb = nh / nw through the torch resize chain (srcmx/Batch_model.py:159-168) */
+int opose_debug_paf_score(opose_t* h, int fast, int n_scales, const float* const* maps, const int* hl, const int* wl,
+                          const int* ga, const int* gb, const int32_t* peak_pos, const int32_t* part_cnt, int N,
+                          int H, int W, double thre2, double* score);
+/* src/body.py:143-155, the greedy matching in stable descending score order: score as above ->
+ * conn_i / conn_j [N,19,cap] int32, conn_s [N,19,cap] (unused slots -1, -1, NaN) and conn_cnt
+ * [N,19] (-1: a part of the limb is empty, the reference's special_k) */
+int opose_debug_limb_greedy(opose_t* h, const double* score, const int32_t* part_cnt, int N, int32_t* conn_i,
+                            int32_t* conn_j, double* conn_s, int32_t* conn_cnt);
+/* src/body.py:157-208, assembly and pruning: records as opose_debug_peaks_finalize leaves them
+ * (status, candidate rows) -> status, n_people and subset rows, in place.  A limb's connections
+ * need not be a matching (the same index may appear twice: the only way to the third-row status
+ * OPOSE_E_ASSEMBLY, src/body.py:170-173).  stage receives the number of connections a frame may
+ * have for the kernel to stage them all at once; beyond, it stages limb by limb */
+int opose_debug_assemble(opose_t* h, void* records, const int32_t* part_cnt, const int32_t* conn_i,
+                         const int32_t* conn_j, const double* conn_s, const int32_t* conn_cnt, int N, int* stage);
 
 #ifdef __cplusplus
 }

@@ -141,8 +141,17 @@ def connect_limbs(all_peaks, paf_avg: np.ndarray, img_h: int, thre2: float):
     return connection_all, special_k
 
 
-def assemble(all_peaks, connection_all, special_k):
-    """Person assembly + pruning (src/body.py:157-212) -> (candidate, subset)."""
+def assemble(all_peaks, connection_all, special_k, trace=None):
+    """Person assembly + pruning (src/body.py:157-212) -> (candidate, subset).
+
+    trace: an optional dict that receives what the run went through (results unchanged): a tally per
+    branch ("new", "skipped_k17", "found1_write", "found1_noop", "merge", "conflict"), "peak_rows"
+    (the most rows alive at once), "merges" ([(row dropped, rows before the drop)]) and "pruned"
+    ([(row, "count" | "mean")]: the first of the two prune conditions that dropped it)."""
+    tr = trace if trace is not None else {}
+    for key in ("new", "skipped_k17", "found1_write", "found1_noop", "merge", "conflict", "peak_rows"):
+        tr[key] = 0
+    tr["merges"], tr["pruned"] = [], []
     candidate = np.array([p for part in all_peaks for p in part])
     people = []                                   # list of float64[20] rows
     for k, (pa, pb) in enumerate(LIMB_SEQ):
@@ -162,6 +171,9 @@ def assemble(all_peaks, connection_all, special_k):
                     row[ib] = id_b
                     row[19] += 1
                     row[18] += candidate[int(id_b), 2] + s
+                    tr["found1_write"] += 1
+                else:
+                    tr["found1_noop"] += 1
             elif len(hits) == 2:
                 r1, r2 = people[hits[0]], people[hits[1]]
                 both = ((r1[:18] >= 0).astype(int) + (r2[:18] >= 0).astype(int)) == 2
@@ -169,17 +181,26 @@ def assemble(all_peaks, connection_all, special_k):
                     r1[:18] += r2[:18] + 1
                     r1[18:] += r2[18:]
                     r1[18] += s
+                    tr["merge"] += 1
+                    tr["merges"].append((hits[1], len(people)))
                     del people[hits[1]]
                 else:
                     r1[ib] = id_b
                     r1[19] += 1
                     r1[18] += candidate[int(id_b), 2] + s
+                    tr["conflict"] += 1
             elif k < 17:
                 row = -1 * np.ones(20)
                 row[ia], row[ib] = id_a, id_b
                 row[19] = 2
                 row[18] = sum(candidate[conn[c, :2].astype(int), 2]) + s
                 people.append(row)
+                tr["new"] += 1
+                tr["peak_rows"] = max(tr["peak_rows"], len(people))
+            else:
+                tr["skipped_k17"] += 1
+    tr["pruned"] = [(i, "count" if r[19] < 4 else "mean") for i, r in enumerate(people)
+                    if r[19] < 4 or r[18] / r[19] < 0.4]
     keep = [r for r in people if not (r[19] < 4 or r[18] / r[19] < 0.4)]
     subset = np.array(keep, dtype=np.float64).reshape(-1, 20) if keep else -1 * np.ones((0, 20))
     return candidate, subset

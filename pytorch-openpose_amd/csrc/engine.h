@@ -298,6 +298,8 @@ ScaleGeom geom(double s, const opose_params& p, int H, int W);
 ScaleGeom geom_from_pads(int hl, int wl, int pad_down, int pad_right, int H, int W);
 void body_post_common(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, const opose_params& p,
                       uint8_t* rec_dev);
+PafScales body_paf_scales(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs);
+PafScales batch_paf_scales(const float* mid, int nh, int nw, int H, int W);
 void batch_resize_chain(opose_ctx* h, int N, int H, int W, const float* maps, int cstride, int hl, int wl, int nh,
                         int nw, float* mid, float* heat);
 void batch_post_common(opose_ctx* h, int N, int H, int W, const float* maps, int cstride, int hl, int wl, int nh,

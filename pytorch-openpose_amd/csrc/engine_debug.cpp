@@ -781,3 +781,172 @@ int opose_debug_batch_hand_label(opose_t* h, const float* heat, int NP, int H, i
     });
     return OPOSE_OK;
 }
+
+// ---- the body matching kernels one at a time (tests/test_gpu_match_stages.py): each hook calls the
+// launcher peaks_to_records calls, with its arguments, at the handle's capacity
+static bool counts_ok(const int32_t* c, size_t n, int lo, int hi) {
+    for (size_t i = 0; i < n; ++i)
+        if (c[i] < lo || c[i] > hi) return false;
+    return true;
+}
+// the first part_cnt positions of every part lie on the H x W map
+static bool positions_ok(const int32_t* pos, const int32_t* pcnt, int N, int cap, int64_t HW) {
+    for (int np = 0; np < N * 18; ++np)
+        for (int i = 0; i < pcnt[np]; ++i) {
+            const int32_t v = pos[(size_t)np * cap + i];
+            if (v < 0 || v >= HW) return false;
+        }
+    return true;
+}
+template <class T>
+static T* to_device(opose_ctx* h, DevBuf& b, const T* src, size_t n) {
+    T* d = b.ensure<T>(n, h->stream);
+    OPOSE_HIP_CHECK(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    return d;
+}
+template <class T>
+static void to_host(opose_ctx* h, T* dst, const T* src, size_t n) {
+    OPOSE_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+}
+
+int opose_debug_peaks_finalize(opose_t* h, const int32_t* cnt, const int32_t* list, const double* score, int N, int H,
+                               int W, void* records, int32_t* peak_pos, int32_t* part_cnt) {
+    if (!h || !cnt || !list || !score || !records || !peak_pos || !part_cnt || N <= 0 || H <= 0 || W <= 0)
+        return OPOSE_E_ARG;
+    const int cap = h->ppp;
+    const int64_t HW = (int64_t)H * W;
+    if (HW > 0x7fffffff) return OPOSE_E_ARG;
+    for (int np = 0; np < N * 18; ++np) {  // the raw count may pass the capacity: the list holds cap entries
+        if (cnt[np] < 0) return OPOSE_E_ARG;
+        for (int i = 0; i < std::min(cnt[np], cap); ++i)
+            if (list[(size_t)np * cap + i] < 0 || list[(size_t)np * cap + i] >= HW) return OPOSE_E_ARG;
+    }
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const RecordLayout L = make_record_layout(h->ppp, h->maxp);
+        const size_t nl = (size_t)N * 18 * cap;
+        DevBuf cb, lb, sb, rb, pb, qb;
+        const int* cd = to_device(h, cb, cnt, (size_t)N * 18);
+        const int* ld = to_device(h, lb, list, nl);
+        const double* sd = to_device(h, sb, score, nl);
+        uint8_t* rec = rb.ensure<uint8_t>(L.bytes * N, h->stream);
+        int* pos = pb.ensure<int>(nl, h->stream);
+        int* pcnt = qb.ensure<int>((size_t)N * 18, h->stream);
+        OPOSE_HIP_CHECK(hipMemsetAsync(rec, 0, L.bytes * N, h->stream));
+        OPOSE_HIP_CHECK(hipMemsetAsync(pos, 0xff, sizeof(int) * nl, h->stream));  // unused slots: -1
+        launch_peaks_finalize(cd, ld, sd, N, H, W, L, rec, pos, pcnt, h->stream);
+        to_host(h, static_cast<uint8_t*>(records), rec, L.bytes * N);
+        to_host(h, peak_pos, pos, nl);
+        to_host(h, part_cnt, pcnt, (size_t)N * 18);
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    });
+    return OPOSE_OK;
+}
+
+int opose_debug_paf_score(opose_t* h, int fast, int n_scales, const float* const* maps, const int* hl, const int* wl,
+                          const int* ga, const int* gb, const int32_t* peak_pos, const int32_t* part_cnt, int N, int H,
+                          int W, double thre2, double* score) {
+    if (!h || !maps || !hl || !wl || !ga || !gb || !peak_pos || !part_cnt || !score || N <= 0 || H <= 0 || W <= 0)
+        return OPOSE_E_ARG;
+    if (n_scales < 1 || n_scales > (fast ? 1 : kMaxScales) || (int64_t)H * W > 0x7fffffff) return OPOSE_E_ARG;
+    for (int s = 0; s < n_scales; ++s) {
+        if (!maps[s] || hl[s] <= 0 || wl[s] <= 0) return OPOSE_E_ARG;
+        if (fast ? (ga[s] <= 0 || gb[s] <= 0 || ga[s] > 8 * hl[s] || gb[s] > 8 * wl[s])
+                 : (ga[s] < 0 || gb[s] < 0 || ga[s] >= 8 * hl[s] || gb[s] >= 8 * wl[s]))
+            return OPOSE_E_ARG;
+    }
+    const int cap = h->ppp;
+    if (!counts_ok(part_cnt, (size_t)N * 18, 0, cap) || !positions_ok(peak_pos, part_cnt, N, cap, (int64_t)H * W))
+        return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        DevBuf mb[kMaxScales], midb, heatb, pb, qb, sb;
+        PafScales S{};
+        if (fast) {
+            const int nh = ga[0], nw = gb[0];
+            const float* md = to_device(h, mb[0], maps[0], (size_t)N * 57 * hl[0] * wl[0]);
+            float* mid = midb.ensure<float>((size_t)N * 56 * nh * nw, h->stream);
+            float* heat = heatb.ensure<float>((size_t)N * 18 * H * W, h->stream);
+            batch_resize_chain(h, N, H, W, md, 57, hl[0], wl[0], nh, nw, mid, heat);
+            S = batch_paf_scales(mid, nh, nw, H, W);
+        } else {
+            std::vector<ScaleGeom> gs;
+            for (int s = 0; s < n_scales; ++s) {
+                const ScaleGeom g = geom_from_pads(hl[s], wl[s], ga[s], gb[s], H, W);
+                body_to_mid(h, s, to_device(h, mb[s], maps[s], (size_t)N * 57 * hl[s] * wl[s]), 57, N, g);
+                gs.push_back(g);
+            }
+            S = body_paf_scales(h, N, H, W, gs);
+        }
+        const size_t ns = (size_t)N * 19 * cap * cap;
+        const int* pos = to_device(h, pb, peak_pos, (size_t)N * 18 * cap);
+        const int* pcnt = to_device(h, qb, part_cnt, (size_t)N * 18);
+        double* sc = sb.ensure<double>(ns, h->stream);
+        OPOSE_HIP_CHECK(hipMemsetAsync(sc, 0xff, sizeof(double) * ns, h->stream));  // a NaN in every unwritten entry
+        launch_paf_score(S, pos, pcnt, N, cap, thre2, sc, h->stream);
+        to_host(h, score, sc, ns);
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_debug_limb_greedy(opose_t* h, const double* score, const int32_t* part_cnt, int N, int32_t* conn_i,
+                            int32_t* conn_j, double* conn_s, int32_t* conn_cnt) {
+    if (!h || !score || !part_cnt || !conn_i || !conn_j || !conn_s || !conn_cnt || N <= 0) return OPOSE_E_ARG;
+    const int cap = h->ppp;
+    if (!counts_ok(part_cnt, (size_t)N * 18, 0, cap)) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const size_t nc = (size_t)N * 19 * cap;
+        DevBuf sb, qb, cb, nb;
+        const double* sc = to_device(h, sb, score, nc * cap);
+        const int* pcnt = to_device(h, qb, part_cnt, (size_t)N * 18);
+        Conn* conn = cb.ensure<Conn>(nc, h->stream);
+        int* ccnt = nb.ensure<int>((size_t)N * 19, h->stream);
+        OPOSE_HIP_CHECK(hipMemsetAsync(conn, 0xff, sizeof(Conn) * nc, h->stream));  // unused slots: -1, -1, NaN
+        launch_limb_greedy(sc, pcnt, N, cap, conn, ccnt, h->stream);
+        std::vector<Conn> hc(nc);
+        to_host(h, hc.data(), conn, nc);
+        to_host(h, conn_cnt, ccnt, (size_t)N * 19);
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        for (size_t e = 0; e < nc; ++e) {
+            conn_i[e] = hc[e].i;
+            conn_j[e] = hc[e].j;
+            conn_s[e] = hc[e].s;
+        }
+    });
+    return OPOSE_OK;
+}
+
+int opose_debug_assemble(opose_t* h, void* records, const int32_t* part_cnt, const int32_t* conn_i,
+                         const int32_t* conn_j, const double* conn_s, const int32_t* conn_cnt, int N, int* stage) {
+    if (!h || !records || !part_cnt || !conn_i || !conn_j || !conn_s || !conn_cnt || !stage || N <= 0) return OPOSE_E_ARG;
+    const int cap = h->ppp;
+    if (!counts_ok(part_cnt, (size_t)N * 18, 0, cap) || !counts_ok(conn_cnt, (size_t)N * 19, -1, cap)) return OPOSE_E_ARG;
+    for (int n = 0; n < N; ++n)
+        for (int k = 0; k < 19; ++k) {
+            const int nA = part_cnt[n * 18 + kHostLimbA[k]], nB = part_cnt[n * 18 + kHostLimbB[k]];
+            for (int c = 0; c < conn_cnt[n * 19 + k]; ++c) {  // (need not be a matching)
+                const size_t e = ((size_t)n * 19 + k) * cap + c;
+                if (conn_i[e] < 0 || conn_i[e] >= nA || conn_j[e] < 0 || conn_j[e] >= nB) return OPOSE_E_ARG;
+            }
+        }
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const RecordLayout L = make_record_layout(h->ppp, h->maxp);
+        *stage = assemble_stage(L);
+        const size_t nc = (size_t)N * 19 * cap;
+        std::vector<Conn> hc(nc);
+        for (size_t e = 0; e < nc; ++e) hc[e] = Conn{conn_i[e], conn_j[e], conn_s[e]};
+        DevBuf rb, qb, cb, nb;
+        uint8_t* rec = to_device(h, rb, static_cast<const uint8_t*>(records), L.bytes * N);
+        const int* pcnt = to_device(h, qb, part_cnt, (size_t)N * 18);
+        const Conn* conn = to_device(h, cb, hc.data(), nc);
+        const int* ccnt = to_device(h, nb, conn_cnt, (size_t)N * 19);
+        launch_assemble(conn, ccnt, pcnt, N, L, rec, h->stream);
+        to_host(h, static_cast<uint8_t*>(records), rec, L.bytes * N);
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    });
+    return OPOSE_OK;
+}

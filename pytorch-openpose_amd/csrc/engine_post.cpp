@@ -116,9 +116,8 @@ static void peaks_to_records(opose_ctx* h, int N, int H, int W, const PafScales&
     h->prof_end(pe);
 }
 
-// post-network body path from per-scale mid sets (body_to_mid) to records
-void body_post_common(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, const opose_params& p,
-                      uint8_t* rec_dev) {
+// what paf_score reads of the per-scale mid sets (body_to_mid): the low-res PAF channels
+PafScales body_paf_scales(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs) {
     const int ns = (int)gs.size();
     PafScales S{};
     for (int s = 0; s < ns; ++s) {
@@ -136,6 +135,14 @@ void body_post_common(opose_ctx* h, int N, int H, int W, const std::vector<Scale
     S.lcm = 38;
     S.H = H;
     S.W = W;
+    return S;
+}
+
+// post-network body path from per-scale mid sets (body_to_mid) to records
+void body_post_common(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, const opose_params& p,
+                      uint8_t* rec_dev) {
+    const int ns = (int)gs.size();
+    const PafScales S = body_paf_scales(h, N, H, W, gs);
     // bytes: the low-res PAF channels, read once from HBM (every sample after the first hits L2)
     double paf_bytes = 0;
     for (int s = 0; s < ns; ++s) paf_bytes += (double)N * 38 * 4 * gs[s].hl * gs[s].wl;
@@ -202,12 +209,9 @@ void batch_resize_chain(opose_ctx* h, int N, int H, int W, const float* maps, in
     h->prof_end(pe);
 }
 
-void batch_post_common(opose_ctx* h, int N, int H, int W, const float* maps, int cstride, int hl, int wl, int nh,
-                       int nw, const opose_params& p, uint8_t* rec_dev) {
-    ProfEntry pe;
-    float* mid = h->mid(0).ensure<float>((size_t)N * 56 * nh * nw, h->stream);
-    float* heat = reinterpret_cast<float*>(h->avg.ensure<double>((size_t)N * 18 * H * W, h->stream));
-    batch_resize_chain(h, N, H, W, maps, cstride, hl, wl, nh, nw, mid, heat);
+// what paf_score reads of batch_resize_chain's mid [N][56][nh][nw]: its PAF channels, resampled to
+// H x W with torch's taps
+PafScales batch_paf_scales(const float* mid, int nh, int nw, int H, int W) {
     PafScales S{};
     S.mid[0] = mid;
     S.hs[0] = nh;
@@ -219,6 +223,16 @@ void batch_post_common(opose_ctx* h, int N, int H, int W, const float* maps, int
     S.H = H;
     S.W = W;
     S.torch = 1;
+    return S;
+}
+
+void batch_post_common(opose_ctx* h, int N, int H, int W, const float* maps, int cstride, int hl, int wl, int nh,
+                       int nw, const opose_params& p, uint8_t* rec_dev) {
+    ProfEntry pe;
+    float* mid = h->mid(0).ensure<float>((size_t)N * 56 * nh * nw, h->stream);
+    float* heat = reinterpret_cast<float*>(h->avg.ensure<double>((size_t)N * 18 * H * W, h->stream));
+    batch_resize_chain(h, N, H, W, maps, cstride, hl, wl, nh, nw, mid, heat);
+    const PafScales S = batch_paf_scales(mid, nh, nw, H, W);
     peaks_to_records(h, N, H, W, S, p, 0, rec_dev, [&](int cap, int* cnt, int* list, double* lscore) {
         h->prof_begin(pe, "gauss_nms", 0, (double)N * 18 * H * W * 4);
         launch_blur5_nms(heat, N * 18, H, W, p.thre1, cap, cnt, list, lscore, h->stream);

@@ -24,6 +24,11 @@ struct PafScales {
     int torch;  // 1: torch bicubic taps (Batch_body fast mode), 0: OpenCV INTER_CUBIC
 };
 
+// src/body.py:97-99: the 19 limbs' parts, 0-based (post.hip's device tables and the host's)
+#define OPOSE_LIMB_A {1, 1, 2, 3, 5, 6, 1, 8, 9, 1, 11, 12, 1, 0, 14, 0, 15, 2, 5}
+#define OPOSE_LIMB_B {2, 5, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 0, 14, 16, 15, 17, 16, 17}
+constexpr int kHostLimbA[19] = OPOSE_LIMB_A, kHostLimbB[19] = OPOSE_LIMB_B;
+
 struct Conn {
     int i, j;
     double s;
@@ -162,6 +167,8 @@ void launch_limb_greedy(const double* score, const int* part_cnt, int N, int cap
                         hipStream_t st);
 void launch_assemble(const Conn* conn, const int* conn_cnt, const int* part_cnt, int N, const RecordLayout& L,
                      uint8_t* records, hipStream_t st);
+// connections assemble_people stages in LDS at once: a frame with more takes them limb by limb
+int assemble_stage(const RecordLayout& L);
 
 // hand.hip
 size_t hand_cc_workspace_bytes(int NP);

@@ -27,8 +27,8 @@ __constant__ double kGauss[13] = {
     0x1.763a210dfb306p-15};
 
 // src/body.py:97-103
-__constant__ int kLimbA[19] = {1, 1, 2, 3, 5, 6, 1, 8, 9, 1, 11, 12, 1, 0, 14, 0, 15, 2, 5};
-__constant__ int kLimbB[19] = {2, 5, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 0, 14, 16, 15, 17, 16, 17};
+__constant__ int kLimbA[19] = OPOSE_LIMB_A;
+__constant__ int kLimbB[19] = OPOSE_LIMB_B;
 __constant__ int kPafX[19] = {12, 20, 14, 16, 22, 24, 0, 2, 4, 6, 8, 10, 28, 30, 34, 32, 36, 18, 26};
 
 // scipy 'reflect' (d c b a | a b c d | d c b a), periodic with period 2n
@@ -1050,15 +1050,20 @@ void launch_limb_greedy(const double* score, const int* part_cnt, int N, int cap
     hipLaunchKernelGGL(limb_greedy, dim3(N * 19), dim3(256), 2 * cap, st, score, part_cnt, cap, conn, conn_cnt);
 }
 
+// staged connection entries of assemble_people: every limb's (19 x peaks_per_part) when that fits
+// 64 KB with the subset rows, at least one limb's
+constexpr size_t kAssembleEntry = 3 * sizeof(double) + 2 * sizeof(int);
+int assemble_stage(const RecordLayout& L) {
+    const size_t sub = sizeof(double) * 20 * L.max_people;
+    const size_t fit = sub < 64 * 1024 ? (64 * 1024 - sub) / kAssembleEntry : 0;
+    return (int)std::max<size_t>((size_t)L.peaks_per_part, std::min<size_t>(19 * (size_t)L.peaks_per_part, fit));
+}
+
 void launch_assemble(const Conn* conn, const int* conn_cnt, const int* part_cnt, int N, const RecordLayout& L,
                      uint8_t* records, hipStream_t st) {
-    // staged connection entries: every limb's (19 x peaks_per_part) when that fits 64 KB with the
-    // subset rows, at least one limb's
-    constexpr size_t kEntry = 3 * sizeof(double) + 2 * sizeof(int);
     const size_t sub = sizeof(double) * 20 * L.max_people;
-    const size_t fit = sub < 64 * 1024 ? (64 * 1024 - sub) / kEntry : 0;
-    const int stage = (int)std::max<size_t>((size_t)L.peaks_per_part, std::min<size_t>(19 * (size_t)L.peaks_per_part, fit));
-    const size_t shm = sub + (size_t)stage * kEntry;
+    const int stage = assemble_stage(L);
+    const size_t shm = sub + (size_t)stage * kAssembleEntry;
     if (shm > 64 * 1024) {  // grown capacities (up to kMaxPeople / kMaxPeaksPerPart: 80 KB)
         static size_t granted = 0;
         if (shm > granted) {

@@ -94,6 +94,10 @@ SIGNATURES = {
     "opose_debug_batch_heat": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "opose_debug_blur5_nms": (_I, [_P, _P, _I, _I, _I, _D, _I, _P, _P, _P]),
     "opose_debug_batch_hand_label": (_I, [_P, _P, _I, _I, _I, _D, _P, _P, _P]),
+    "opose_debug_peaks_finalize": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "opose_debug_paf_score": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _P]),
+    "opose_debug_limb_greedy": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "opose_debug_assemble": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
 }
 EXPORTED = list(SIGNATURES)
 
