@@ -168,6 +168,23 @@ int opose_body_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W,
                      int64_t row_stride, int64_t frame_stride, const opose_params* p,
                      void* records, int flags);
 
+/* Body.__call__ (src/body.py:24-212) for n_groups groups of frames in one lockstep pass: group g is
+ * N[g] frames uint8 [H[g]][W[g]][3] at bgr[g] with strides row_stride[g] / frame_stride[g] (bytes),
+ * records[g] receives its N[g] records.  Replaces a loop of Body.__call__ over frames of different
+ * sizes (a folder of photographs, several cameras): every (group, scale) pair is one segment of the
+ * network's launches, so a conv launch per layer covers all of them, and one preprocess launch
+ * reads every group's frames.  A group's records are those opose_body_infer gives for that group
+ * alone, bit for bit, whatever runs beside it: a conv sums a pixel in an order fixed by the layer
+ * and the group's own N x H x W.  n_groups * p->n_scales <= OPOSE_MAX_SCALES.
+ * OPOSE_IN_DEVICE / OPOSE_OUT_DEVICE as opose_body_infer (every bgr[g] / every records[g]; the
+ * pointer arrays themselves are host memory, read before the call returns); OPOSE_PIPELINE is not
+ * taken (OPOSE_E_ARG).  Returns the worst per-frame status of all groups.  The fp32 path
+ * (OPOSE_CONV=f32) and OPOSE_LOCKSTEP=0 run the groups one after another. */
+int opose_body_infer_groups(opose_t* h, int n_groups, const uint8_t* const* bgr, const int* N,
+                            const int* H, const int* W, const int64_t* row_stride,
+                            const int64_t* frame_stride, const opose_params* p,
+                            void* const* records, int flags);
+
 /* Post-network body path on a single scale (what follows src/body.py:50):
  * maps [N,57,h,w] fp32 (channels 0..37 PAF, 38..56 heat), padded net input (h*8, w*8),
  * pad_down / pad_right as util.padRightDownCorner, frame H x W. */
@@ -408,6 +425,12 @@ int opose_debug_conv_x6_time(opose_t* h, int N, int Cin, int H, int W, int Cout,
  * (out may be NULL to query the size) */
 int opose_debug_preprocess(opose_t* h, const uint8_t* bgr, int H, int W, double scale, int pad_value,
                            float* out, int* HpWp);
+/* The same for n_groups <= OPOSE_MAX_SCALES groups of N[g] dense frames [N[g],H[g],W[g],3] through
+ * the one-launch form opose_body_infer_groups uses (preprocess_u8_segs): out[g] [N[g],3,Hp,Wp],
+ * HpWp [n_groups][2] (out, or any out[g], may be NULL to query the sizes only) */
+int opose_debug_preprocess_groups(opose_t* h, int n_groups, const uint8_t* const* bgr, const int* N,
+                                  const int* H, const int* W, double scale, int pad_value,
+                                  float* const* out, int* HpWp);
 /* src/body.py:54-57,67 for one frame: maps [57,hl,wl] -> heat_avg [18,H,W] float64 and
  * (optional) the x8-upsampled, cropped PAF maps [38,Hs,Ws] float32 */
 int opose_debug_heat(opose_t* h, const float* maps, int hl, int wl, int pad_down, int pad_right, int H, int W,

@@ -296,9 +296,11 @@ float* net_forward(opose_ctx* h, int net, const float* x, int N, int Hp, int Wp)
 // engine_post.cpp
 ScaleGeom geom(double s, const opose_params& p, int H, int W);
 ScaleGeom geom_from_pads(int hl, int wl, int pad_down, int pad_right, int H, int W);
+// slot0: the mid set of the frames' first scale (scale s in set slot0 + s; one group of frames: 0)
 void body_post_common(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, const opose_params& p,
-                      uint8_t* rec_dev);
-PafScales body_paf_scales(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs);
+                      uint8_t* rec_dev, int slot0 = 0);
+void body_post_reserve(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, int slot0);
+PafScales body_paf_scales(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, int slot0 = 0);
 PafScales batch_paf_scales(const float* mid, int nh, int nw, int H, int W);
 void batch_resize_chain(opose_ctx* h, int N, int H, int W, const float* maps, int cstride, int hl, int wl, int nh,
                         int nw, float* mid, float* heat);
@@ -313,6 +315,7 @@ void body_to_mid(opose_ctx* h, int s, const float* maps, int cstride, int N, con
 void hand_finish(opose_ctx* h, int N, double* peaks_out, int32_t* found_out, int flags);
 uint8_t* records_dest(opose_ctx* h, int N, void* records, int flags);
 int finish_records(opose_ctx* h, int N, void* records, uint8_t* rec_dev, int flags);
+int finish_records_groups(opose_ctx* h, int n, const int* N, void* const* records, uint8_t* const* rec_dev, int flags);
 // engine_api.cpp
 void flush_post(opose_ctx* h);
 void enter_main(opose_ctx* h);
@@ -320,6 +323,9 @@ const uint8_t* stage_frames(opose_ctx* h, const uint8_t* bgr, int N, int H, int 
                             int64_t frame_stride, int flags);
 void preprocess_scale(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
                       const ScaleGeom& g, const opose_params& p, float* x, hipStream_t stream);
+PrepSeg prep_seg(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
+                 const ScaleGeom& g, float* x);
+void preprocess_segs(opose_ctx* h, PrepTable& t, int nseg, const opose_params& p);
 BatchGeom batch_geom(const opose_params& p, int H, int W);
 void batch_preprocess(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
                       const BatchGeom& g, float* x, hipStream_t stream);
@@ -418,6 +424,9 @@ struct opose_ctx {
         const char* e = getenv("OPOSE_EXTRACT_CHUNK");
         return e ? std::atoi(e) : 0;
     }();
+    // the segment table of the last launch_preprocess_segs (kPrepSegs rows; written on the stream
+    // right before the launch that reads it)
+    opose::DevBuf prep_table;
     opose::PinnedBuf hand_out;  // Hand() peaks + found, staged for the host
     // network workspace, one set per concurrently running scale (slot s runs on scale_stream(s);
     // slot 0 is the handle's stream): input, activations, k-slab partials

@@ -38,6 +38,36 @@ void preprocess_scale(const uint8_t* frames, int64_t frame_stride, int64_t row_s
                       (float)p.pad_value / 256.f - 0.5f, x, stream);
 }
 
+// preprocess_scale's arguments as one segment's row of a preprocess table (kernels.h PrepSeg)
+PrepSeg prep_seg(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
+                 const ScaleGeom& g, float* x) {
+    PrepSeg s{};
+    s.src = frames;
+    s.out = x;
+    s.frame_stride = frame_stride;
+    s.row_stride = row_stride;
+    s.sy = s.sx = 1.0 / g.mult;
+    s.N = N;
+    s.H = H;
+    s.W = W;
+    s.Hs = g.Hs;
+    s.Ws = g.Ws;
+    s.Hp = g.Hp;
+    s.Wp = g.Wp;
+    return s;
+}
+
+// preprocess_scale of every segment of the table in one launch, through the handle's device table
+void preprocess_segs(opose_ctx* h, PrepTable& t, int nseg, const opose_params& p) {
+    PrepSeg* dev = h->prep_table.ensure<PrepSeg>(kPrepSegs, h->stream);
+    ProfEntry pe;
+    double bytes = 0;
+    for (int k = 0; k < nseg; ++k) bytes += (double)t.s[k].N * (3.0 * t.s[k].H * t.s[k].W + 12.0 * t.s[k].Hp * t.s[k].Wp);
+    h->prof_begin(pe, "preprocess", 0, bytes);
+    launch_preprocess_segs(t, nseg, (float)p.pad_value / 256.f - 0.5f, dev, h->stream);
+    h->prof_end(pe);
+}
+
 // Batch_body.calculate_size_pad (srcmx/Batch_model.py:302-307): int() truncation
 BatchGeom batch_geom(const opose_params& p, int H, int W) {
     BatchGeom g;
@@ -438,6 +468,84 @@ int opose_body_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_
             });
         }
         return finish_records(h, N, records, rec, flags);
+    });
+}
+
+int opose_body_infer_groups(opose_t* h, int n_groups, const uint8_t* const* bgr, const int* N, const int* H,
+                            const int* W, const int64_t* row_stride, const int64_t* frame_stride,
+                            const opose_params* pp, void* const* records, int flags) {
+    if (!h || !bgr || !N || !H || !W || !row_stride || !frame_stride || !records) return OPOSE_E_ARG;
+    if (n_groups < 1 || n_groups > OPOSE_MAX_SCALES || (flags & (OPOSE_PIPELINE | OPOSE_PIPELINE_DEFER)))
+        return OPOSE_E_ARG;
+    for (int g = 0; g < n_groups; ++g) {
+        if (!bgr[g] || !records[g] || N[g] <= 0 || H[g] <= 0 || W[g] <= 0) return OPOSE_E_ARG;
+        if (row_stride[g] < (int64_t)W[g] * 3 || frame_stride[g] < row_stride[g] * H[g]) return OPOSE_E_ARG;
+    }
+    if (pp && pp->n_scales >= 1 && (int64_t)n_groups * pp->n_scales > OPOSE_MAX_SCALES) return OPOSE_E_ARG;
+    if (!(h->x6 && h->lockstep)) {
+        // no lockstep (fp32 path, OPOSE_LOCKSTEP=0): the groups one after another, each as its own call
+        int worst = OPOSE_OK;
+        for (int g = 0; g < n_groups; ++g) {
+            const int rc = opose_body_infer(h, bgr[g], N[g], H[g], W[g], row_stride[g], frame_stride[g], pp, records[g],
+                                            flags);
+            if (rc != OPOSE_OK && rc != OPOSE_E_CAPACITY && rc != OPOSE_E_ASSEMBLY) return rc;
+            worst = std::min(worst, rc);
+        }
+        return worst;
+    }
+    OPOSE_TRY(h, {
+        const opose_params p = fill_params(pp, OPOSE_NET_BODY);
+        const int ns = p.n_scales, nseg = n_groups * ns;
+        enter_main(h);
+        h->mid_set = 0;
+        if (!h->loaded[OPOSE_NET_BODY]) throw std::runtime_error("body weights not loaded");
+        const bool id = flags & OPOSE_IN_DEVICE, od = flags & OPOSE_OUT_DEVICE;
+        const size_t rbytes = make_record_layout(h->ppp, h->maxp).bytes;
+        std::vector<std::vector<ScaleGeom>> gs(n_groups);
+        for (int g = 0; g < n_groups; ++g)
+            for (int s = 0; s < ns; ++s) gs[g].push_back(geom(p.scales[s], p, H[g], W[g]));
+        // Every buffer of the call at its full size before anything is enqueued: a buffer that grew
+        // between two groups would synchronise the device and drop what the earlier groups left.
+        // Segment (g, s) has workspace and mid set g * ns + s.
+        std::vector<size_t> foff(n_groups + 1, 0), roff(n_groups + 1, 0);
+        for (int g = 0; g < n_groups; ++g) {
+            foff[g + 1] = foff[g] + (size_t)frame_stride[g] * N[g];
+            roff[g + 1] = roff[g] + rbytes * N[g];
+        }
+        uint8_t* fbuf = id ? nullptr : h->frames.ensure<uint8_t>(foff[n_groups], h->stream);
+        uint8_t* rbuf = od ? nullptr : h->records.ensure<uint8_t>(roff[n_groups], h->stream);
+        h->prep_table.ensure<PrepSeg>(kPrepSegs, h->stream);
+        PrepTable table{};
+        std::vector<NetSeg> segs;
+        std::vector<const uint8_t*> fd(n_groups);
+        std::vector<uint8_t*> rec(n_groups);
+        for (int g = 0; g < n_groups; ++g) {
+            fd[g] = id ? bgr[g] : fbuf + foff[g];
+            rec[g] = od ? static_cast<uint8_t*>(records[g]) : rbuf + roff[g];
+            body_post_reserve(h, N[g], H[g], W[g], gs[g], g * ns);
+            for (int s = 0; s < ns; ++s) {
+                const ScaleGeom& sg = gs[g][s];
+                float* x = h->ws[g * ns + s].x.ensure<float>((size_t)N[g] * 3 * sg.Hp * sg.Wp, h->stream);
+                table.s[g * ns + s] = prep_seg(fd[g], frame_stride[g], row_stride[g], N[g], H[g], W[g], sg, x);
+                segs.push_back(NetSeg{x, N[g], sg.Hp, sg.Wp, g * ns + s});
+            }
+        }
+        std::string key;
+        for (int g = 0; g < n_groups; ++g) {
+            if (!id)
+                OPOSE_HIP_CHECK(hipMemcpyAsync(fbuf + foff[g], bgr[g], host_span(N[g], H[g], W[g], row_stride[g], frame_stride[g]),
+                                               hipMemcpyHostToDevice, h->stream));
+            key += call_key(g ? "" : "body_groups", N[g], H[g], W[g], row_stride[g], frame_stride[g], p, fd[g], rec[g],
+                            h->ppp, h->maxp);
+        }
+        run_graphed(h, key, [&] {
+            preprocess_segs(h, table, nseg, p);
+            const std::vector<float*> outs = net_forward_x6(h, OPOSE_NET_BODY, segs);
+            for (int g = 0; g < n_groups; ++g)
+                for (int s = 0; s < ns; ++s) body_to_mid(h, g * ns + s, outs[g * ns + s], 185, N[g], gs[g][s]);
+            for (int g = 0; g < n_groups; ++g) body_post_common(h, N[g], H[g], W[g], gs[g], p, rec[g], g * ns);
+        });
+        return finish_records_groups(h, n_groups, N, records, rec.data(), flags);
     });
 }
 

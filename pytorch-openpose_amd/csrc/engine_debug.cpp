@@ -638,6 +638,44 @@ int opose_debug_preprocess(opose_t* h, const uint8_t* bgr, int H, int W, double 
     return OPOSE_OK;
 }
 
+int opose_debug_preprocess_groups(opose_t* h, int n_groups, const uint8_t* const* bgr, const int* N, const int* H,
+                                  const int* W, double scale, int pad_value, float* const* out, int* HpWp) {
+    if (!h || !bgr || !N || !H || !W || !HpWp || n_groups < 1 || n_groups > OPOSE_MAX_SCALES) return OPOSE_E_ARG;
+    for (int g = 0; g < n_groups; ++g)
+        if (!bgr[g] || N[g] <= 0 || H[g] <= 0 || W[g] <= 0) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        opose_params p;
+        opose_default_params(OPOSE_NET_BODY, &p);
+        p.pad_value = pad_value;
+        std::vector<ScaleGeom> gs;
+        bool run = out != nullptr;
+        for (int g = 0; g < n_groups; ++g) {
+            gs.push_back(geom(scale, p, H[g], W[g]));
+            HpWp[2 * g] = gs[g].Hp;
+            HpWp[2 * g + 1] = gs[g].Wp;
+            run = run && out[g];
+        }
+        if (!run) return OPOSE_OK;
+        std::vector<DevBuf> fin(n_groups), xo(n_groups);
+        PrepTable table{};
+        for (int g = 0; g < n_groups; ++g) {
+            const size_t fb = (size_t)H[g] * W[g] * 3;
+            uint8_t* fd = fin[g].ensure<uint8_t>(fb * N[g], h->stream);
+            float* xd = xo[g].ensure<float>((size_t)N[g] * 3 * gs[g].Hp * gs[g].Wp, h->stream);
+            OPOSE_HIP_CHECK(hipMemcpyAsync(fd, bgr[g], fb * N[g], hipMemcpyHostToDevice, h->stream));
+            table.s[g] = prep_seg(fd, (int64_t)fb, (int64_t)W[g] * 3, N[g], H[g], W[g], gs[g], xd);
+        }
+        preprocess_segs(h, table, n_groups, p);
+        for (int g = 0; g < n_groups; ++g)
+            OPOSE_HIP_CHECK(hipMemcpyAsync(out[g], table.s[g].out, (size_t)N[g] * 3 * gs[g].Hp * gs[g].Wp * 4,
+                                           hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
 // maps [57][hl][wl] -> heat_avg [18][H][W] (float64) and PAF x8 map [38][Hs][Ws] (float32)
 int opose_debug_heat(opose_t* h, const float* maps, int hl, int wl, int pad_down, int pad_right, int H, int W,
                      double* heat_avg, float* paf_mid) {

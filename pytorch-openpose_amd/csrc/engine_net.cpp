@@ -302,7 +302,12 @@ static void run_chain_x6(opose_ctx* h, const std::vector<ChainSeg>& segs) {
             return;
         }
     }
-    bool fuse = h->fuse1x1 && !segs.empty() && segs.size() <= (size_t)kX6Groups && !small_pair(segs[0]);
+    if (segs.size() > (size_t)kX6Groups) {  // more pairs than a launch has groups (five or more body segments)
+        for (size_t i = 0; i < segs.size(); i += kX6Groups)
+            run_chain_x6(h, std::vector<ChainSeg>(segs.begin() + i, segs.begin() + std::min(segs.size(), i + (size_t)kX6Groups)));
+        return;
+    }
+    bool fuse = h->fuse1x1 && !segs.empty() && !small_pair(segs[0]);
     for (const ChainSeg& sg : segs) {
         const DevConv *c1 = sg.c1, *c2 = sg.c2;
         fuse = fuse && c1->ks == 1 && c2->ks == 1 && c1->cin_g == 16 && c1->cout == c1->Mpad && c1->Mpad % 128 == 0 &&

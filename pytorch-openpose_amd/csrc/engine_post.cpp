@@ -48,11 +48,13 @@ static size_t body_mid_heat(int N, const ScaleGeom& g) { return (size_t)N * 18 *
 // one launch with the average written once (heat_full_scales) where the handle allows it and the
 // scales fit, else a launch per scale; f32: one scale, whose average is exactly its float32
 // resize -> avg holds a float map.  mid_per_scale: the per-scale profile entries also book the
-// mid bytes they read (the body path's do, the hand path's do not).
+// mid bytes they read (the body path's do, the hand path's do not).  slot0: the mid set of scale 0.
 static void heat_average(opose_ctx* h, int N, int C, int frame0, int H, int W, const std::vector<ScaleGeom>& gs,
-                         bool f32, bool mid_per_scale, double* avg) {
+                         bool f32, bool mid_per_scale, double* avg, int slot0 = 0) {
     const int ns = (int)gs.size();
-    auto mid = [&](int s) { return h->mid(s).ensure<float>(0, h->stream) + (size_t)frame0 * C * gs[s].Hs * gs[s].Ws; };
+    auto mid = [&](int s) {
+        return h->mid(slot0 + s).ensure<float>(0, h->stream) + (size_t)frame0 * C * gs[s].Hs * gs[s].Ws;
+    };
     ProfEntry pe;
     HeatScales hsc{};
     hsc.n = ns;
@@ -82,6 +84,29 @@ static void heat_average(opose_ctx* h, int N, int C, int frame0, int H, int W, c
     }
 }
 
+// the peak-list and matching workspace of N frames at the handle's capacity
+struct PeakWS {
+    int *cnt, *list;
+    double* lscore;
+    int *pos, *pcnt;
+    double* score;
+    Conn* conn;
+    int* ccnt;
+};
+static PeakWS peak_ws(opose_ctx* h, int N) {
+    const int cap = h->ppp;
+    PeakWS w;
+    w.cnt = h->cnt.ensure<int>((size_t)N * 18, h->stream);
+    w.list = h->list.ensure<int>((size_t)N * 18 * cap, h->stream);
+    w.lscore = h->list_score.ensure<double>((size_t)N * 18 * cap, h->stream);
+    w.pos = h->peak_pos.ensure<int>((size_t)N * 18 * cap, h->stream);
+    w.pcnt = h->part_cnt.ensure<int>((size_t)N * 18, h->stream);
+    w.score = h->score.ensure<double>((size_t)N * 19 * cap * cap, h->stream);
+    w.conn = h->conn.ensure<Conn>((size_t)N * 19 * cap, h->stream);
+    w.ccnt = h->conn_cnt.ensure<int>((size_t)N * 19, h->stream);
+    return w;
+}
+
 // Second half of the body post path, shared by Body (body_post_common) and Batch_body
 // (batch_post_common): the peak-list and matching workspace, then find_peaks(cap, cnt, list, lscore)
 // (the caller's NMS over its part maps), then peaks_finalize .. assemble into the records.
@@ -91,14 +116,10 @@ static void peaks_to_records(opose_ctx* h, int N, int H, int W, const PafScales&
                              double paf_bytes, uint8_t* rec_dev, F&& find_peaks) {
     const RecordLayout L = make_record_layout(h->ppp, h->maxp);
     const int cap = h->ppp;
-    int* cnt = h->cnt.ensure<int>((size_t)N * 18, h->stream);
-    int* list = h->list.ensure<int>((size_t)N * 18 * cap, h->stream);
-    double* lscore = h->list_score.ensure<double>((size_t)N * 18 * cap, h->stream);
-    int* pos = h->peak_pos.ensure<int>((size_t)N * 18 * cap, h->stream);
-    int* pcnt = h->part_cnt.ensure<int>((size_t)N * 18, h->stream);
-    double* score = h->score.ensure<double>((size_t)N * 19 * cap * cap, h->stream);
-    Conn* conn = h->conn.ensure<Conn>((size_t)N * 19 * cap, h->stream);
-    int* ccnt = h->conn_cnt.ensure<int>((size_t)N * 19, h->stream);
+    const PeakWS w = peak_ws(h, N);
+    int *cnt = w.cnt, *list = w.list, *pos = w.pos, *pcnt = w.pcnt, *ccnt = w.ccnt;
+    double *lscore = w.lscore, *score = w.score;
+    Conn* conn = w.conn;
     OPOSE_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * N * 18, h->stream));
     find_peaks(cap, cnt, list, lscore);
     ProfEntry pe;
@@ -116,12 +137,12 @@ static void peaks_to_records(opose_ctx* h, int N, int H, int W, const PafScales&
     h->prof_end(pe);
 }
 
-// what paf_score reads of the per-scale mid sets (body_to_mid): the low-res PAF channels
-PafScales body_paf_scales(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs) {
+// what paf_score reads of the per-scale mid sets (body_to_mid) slot0 .. : the low-res PAF channels
+PafScales body_paf_scales(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, int slot0) {
     const int ns = (int)gs.size();
     PafScales S{};
     for (int s = 0; s < ns; ++s) {
-        S.mid[s] = h->mid(s).ensure<float>(0, h->stream);
+        S.mid[s] = h->mid(slot0 + s).ensure<float>(0, h->stream);
         S.low[s] = S.mid[s] + body_mid_heat(N, gs[s]);
         S.hs[s] = gs[s].Hs;
         S.ws[s] = gs[s].Ws;
@@ -138,11 +159,27 @@ PafScales body_paf_scales(opose_ctx* h, int N, int H, int W, const std::vector<S
     return S;
 }
 
-// post-network body path from per-scale mid sets (body_to_mid) to records
+// body_post_common's single-scale form with the heat resize inside the NMS tiles: no average map
+static bool body_post_resizes_in_nms(int H, int W, const std::vector<ScaleGeom>& gs) {
+    return gs.size() == 1 && gauss_nms_resize_fits(gs[0].Hs, gs[0].Ws, H, W, gs[0].up_sy);
+}
+
+// Every buffer body_to_mid (into mid sets slot0 ..) and body_post_common need for N frames of
+// H x W, allocated now: a call that runs several groups of frames (opose_body_infer_groups) sizes
+// them for every group before it enqueues anything, since a buffer that grows synchronises the
+// device and loses its contents.
+void body_post_reserve(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, int slot0) {
+    for (size_t s = 0; s < gs.size(); ++s)
+        h->mid(slot0 + (int)s).ensure<float>(body_mid_heat(N, gs[s]) + (size_t)N * 38 * gs[s].hl * gs[s].wl, h->stream);
+    peak_ws(h, N);
+    if (!body_post_resizes_in_nms(H, W, gs)) h->avg.ensure<double>((size_t)N * 18 * H * W, h->stream);
+}
+
+// post-network body path from per-scale mid sets (body_to_mid; scale s in set slot0 + s) to records
 void body_post_common(opose_ctx* h, int N, int H, int W, const std::vector<ScaleGeom>& gs, const opose_params& p,
-                      uint8_t* rec_dev) {
+                      uint8_t* rec_dev, int slot0) {
     const int ns = (int)gs.size();
-    const PafScales S = body_paf_scales(h, N, H, W, gs);
+    const PafScales S = body_paf_scales(h, N, H, W, gs, slot0);
     // bytes: the low-res PAF channels, read once from HBM (every sample after the first hits L2)
     double paf_bytes = 0;
     for (int s = 0; s < ns; ++s) paf_bytes += (double)N * 38 * 4 * gs[s].hl * gs[s].wl;
@@ -150,7 +187,7 @@ void body_post_common(opose_ctx* h, int N, int H, int W, const std::vector<Scale
         ProfEntry pe;
         // single scale: the float64 average equals the float32 resize output exactly -> f32 map
         const bool f32 = ns == 1;
-        if (f32 && gauss_nms_resize_fits(gs[0].Hs, gs[0].Ws, H, W, gs[0].up_sy)) {
+        if (body_post_resizes_in_nms(H, W, gs)) {
             // one scale, a true upsampling resize (the reference's 368-row frames at scale 0.5): the
             // resize runs inside the NMS tiles (post.hip gauss_nms_resize) and tiles whose sources
             // cannot produce a peak are dropped, so no full-resolution map is written or read.
@@ -165,7 +202,7 @@ void body_post_common(opose_ctx* h, int N, int H, int W, const std::vector<Scale
             return;
         }
         double* avg = h->avg.ensure<double>((size_t)N * 18 * H * W, h->stream);
-        heat_average(h, N, 18, 0, H, W, gs, f32, true, avg);
+        heat_average(h, N, 18, 0, H, W, gs, f32, true, avg, slot0);
         h->prof_begin(pe, "gauss_nms", 0, (double)N * 18 * H * W * (f32 ? 4 : 8));
         launch_gauss_nms(avg, f32, N * 18, H, W, p.thre1, cap, cnt, list, lscore, h->stream);
         h->prof_end(pe);
@@ -333,6 +370,24 @@ static int worst_status(const uint8_t* rec, int N, size_t bytes) {
 uint8_t* records_dest(opose_ctx* h, int N, void* records, int flags) {
     if (flags & OPOSE_OUT_DEVICE) return static_cast<uint8_t*>(records);
     return h->records.ensure<uint8_t>(make_record_layout(h->ppp, h->maxp).bytes * N, h->stream);
+}
+
+// finish_records for the n groups of one call (group g: N[g] records at rec_dev[g] for records[g]):
+// every copy, then one wait; the worst status of all
+int finish_records_groups(opose_ctx* h, int n, const int* N, void* const* records, uint8_t* const* rec_dev,
+                          int flags) {
+    const RecordLayout L = make_record_layout(h->ppp, h->maxp);
+    const bool od = flags & OPOSE_OUT_DEVICE;
+    for (int g = 0; g < n; ++g)
+        if (rec_dev[g] != records[g])
+            OPOSE_HIP_CHECK(hipMemcpyAsync(records[g], rec_dev[g], L.bytes * N[g],
+                                           od ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    if (!od) OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->prof_drain();
+    int worst = OPOSE_OK;
+    if (!od)
+        for (int g = 0; g < n; ++g) worst = std::min(worst, worst_status(static_cast<const uint8_t*>(records[g]), N[g], L.bytes));
+    return worst;
 }
 
 int finish_records(opose_ctx* h, int N, void* records, uint8_t* rec_dev, int flags) {

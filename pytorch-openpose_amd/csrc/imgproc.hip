@@ -17,17 +17,16 @@
 
 namespace opose {
 
-// uint8 cubic resize (fixed point, coefficients x2048, (v + 2^21) >> 22) + pad + normalise.
-__global__ __launch_bounds__(256) void preprocess_u8(const uint8_t* __restrict__ src, int64_t frame_stride,
-                                                     int64_t row_stride, int H, int W, int Hs, int Ws,
-                                                     double scale_y, double scale_x, int Hp, int Wp,
-                                                     float pad_val, float* __restrict__ out) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    const int n = blockIdx.z;
+// uint8 cubic resize (fixed point, coefficients x2048, (v + 2^21) >> 22) + pad + normalise: pixel
+// (x, y) of one frame f [H][W][3] into its three planes of out [3][Hp][Wp].  The one statement of
+// this arithmetic: preprocess_u8 and preprocess_u8_segs differ only in how a workgroup finds its
+// frame and row.
+__device__ __forceinline__ void preprocess_pixel(const uint8_t* __restrict__ f, int64_t row_stride, int H, int W,
+                                                 int Hs, int Ws, double scale_y, double scale_x, int Hp, int Wp,
+                                                 float pad_val, float* __restrict__ out, int x, int y) {
     if (x >= Wp) return;
     const size_t plane = (size_t)Hp * Wp;
-    float* o = out + (size_t)n * 3 * plane + (size_t)y * Wp + x;
+    float* o = out + (size_t)y * Wp + x;
     if (y >= Hs || x >= Ws) {
         o[0] = pad_val;
         o[plane] = pad_val;
@@ -42,7 +41,6 @@ __global__ __launch_bounds__(256) void preprocess_u8(const uint8_t* __restrict__
         ia[j] = coef_short(tx.c[j]);
         ib[j] = coef_short(ty.c[j]);
     }
-    const uint8_t* f = src + (size_t)n * frame_stride;
     int acc[3] = {0, 0, 0};
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -65,6 +63,40 @@ __global__ __launch_bounds__(256) void preprocess_u8(const uint8_t* __restrict__
         v = v < 0 ? 0 : (v > 255 ? 255 : v);
         o[(size_t)c * plane] = (float)v / 256.f - 0.5f;
     }
+}
+
+// a workgroup: 256 columns of row blockIdx.y of frame blockIdx.z (adjacent lanes read adjacent
+// source pixels and write adjacent floats of each plane)
+__global__ __launch_bounds__(256) void preprocess_u8(const uint8_t* __restrict__ src, int64_t frame_stride,
+                                                     int64_t row_stride, int H, int W, int Hs, int Ws,
+                                                     double scale_y, double scale_x, int Hp, int Wp,
+                                                     float pad_val, float* __restrict__ out) {
+    const int n = blockIdx.z;
+    preprocess_pixel(src + (size_t)n * frame_stride, row_stride, H, W, Hs, Ws, scale_y, scale_x, Hp, Wp, pad_val,
+                     out + (size_t)n * 3 * Hp * Wp, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y);
+}
+
+// The same for every segment of a lockstep pass (opose_body_infer_groups: a segment is one scale of
+// one group of equally sized frames) in one launch: a 1-D grid of preprocess_u8's workgroups, the
+// segments' one after another.  A workgroup finds its segment by the running block count in the
+// table (wave-uniform, at most kPrepSegs entries), then its frame, row and 256-column run in it.
+// the first `words` 32-bit words of the table (a kernel argument) to device memory, a word per lane
+__global__ __launch_bounds__(64) void prep_table_store(PrepTable t, int words, uint32_t* __restrict__ dst) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < words) dst[i] = reinterpret_cast<const uint32_t*>(&t)[i];
+}
+
+__global__ __launch_bounds__(256) void preprocess_u8_segs(const PrepSeg* __restrict__ table, int nseg, float pad_val) {
+    const int b = blockIdx.x;
+    int k = 0;
+    while (k + 1 < nseg && b >= table[k].block_end) ++k;
+    const PrepSeg s = table[k];
+    const int local = b - (k ? table[k - 1].block_end : 0);
+    const int rows = local / s.bx;  // (frame, row) pairs before this one
+    const int n = rows / s.Hp;
+    preprocess_pixel(s.src + (size_t)n * s.frame_stride, s.row_stride, s.H, s.W, s.Hs, s.Ws, s.sy, s.sx, s.Hp, s.Wp,
+                     pad_val, s.out + (size_t)n * 3 * s.Hp * s.Wp, (local - rows * s.bx) * 256 + threadIdx.x,
+                     rows - n * s.Hp);
 }
 
 // cubic resize of mid [N][Cm][Hs][Ws] channels [coff, coff+P) to [H][W], then
@@ -257,6 +289,25 @@ void launch_preprocess(const uint8_t* src, int64_t frame_stride, int64_t row_str
     dim3 grid((Wp + 255) / 256, Hp, N);
     hipLaunchKernelGGL(preprocess_u8, grid, dim3(256), 0, st, src, frame_stride, row_stride, H, W, Hs, Ws, sy, sx, Hp,
                        Wp, pad_val, out);
+}
+
+void launch_preprocess_segs(PrepTable& t, int nseg, float pad_val, PrepSeg* table_dev, hipStream_t st) {
+    if (nseg < 1 || nseg > kPrepSegs) throw std::invalid_argument("preprocess: 1 .. 8 segments");
+    int64_t end = 0;
+    for (int k = 0; k < nseg; ++k) {
+        PrepSeg& s = t.s[k];
+        if (s.N < 1 || s.H < 1 || s.W < 1 || s.Hp < 1 || s.Wp < 1 || s.Hs > s.Hp || s.Ws > s.Wp)
+            throw std::invalid_argument("preprocess: empty segment");
+        s.bx = (s.Wp + 255) / 256;
+        end += (int64_t)s.N * s.Hp * s.bx;
+        if (end > 0x7fffffff) throw std::invalid_argument("preprocess: more workgroups than a grid holds");
+        s.block_end = (int)end;
+        s.reserved = 0;
+    }
+    const int words = nseg * (int)(sizeof(PrepSeg) / 4);
+    hipLaunchKernelGGL(prep_table_store, dim3((words + 63) / 64), dim3(64), 0, st, t, words,
+                       reinterpret_cast<uint32_t*>(table_dev));
+    hipLaunchKernelGGL(preprocess_u8_segs, dim3((unsigned)end), dim3(256), 0, st, table_dev, nseg, pad_val);
 }
 
 void launch_upsample8(const float* in, int in_cstride, int in_coff, int C, int N, int hl, int wl, int Hs, int Ws,

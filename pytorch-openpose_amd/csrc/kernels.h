@@ -99,6 +99,28 @@ void launch_conv_wino_x6(const X6Args& a, hipStream_t st);
 // imgproc.hip
 void launch_preprocess(const uint8_t* src, int64_t frame_stride, int64_t row_stride, int N, int H, int W, int Hs,
                        int Ws, double sy, double sx, int Hp, int Wp, float pad_val, float* out, hipStream_t st);
+// launch_preprocess for up to kPrepSegs segments, each with its own frames and geometry, in one
+// launch (preprocess_u8_segs).  A segment's row of the table, which the kernel reads from device
+// memory: launch_preprocess's arguments, then what prep_table_blocks fills in.
+constexpr int kPrepSegs = kMaxScales;
+struct PrepSeg {
+    const uint8_t* src;  // N frames [H][W][3]
+    float* out;          // [N][3][Hp][Wp]
+    int64_t frame_stride, row_stride;
+    double sy, sx;
+    int N, H, W, Hs, Ws, Hp, Wp;
+    int bx;         // workgroups per output row
+    int block_end;  // workgroups of this and every earlier segment
+    int reserved;   // (no padding bytes: the struct travels as kernel argument words)
+};
+struct PrepTable {
+    PrepSeg s[kPrepSegs];
+};
+// Checks the segments t.s[0 .. nseg) and fills their bx / block_end, writes the table to table_dev
+// (kPrepSegs rows of device memory) with a store kernel and launches preprocess_u8_segs on it: two
+// launches on st, with nothing read from host memory after the call returns (a stream capture
+// replays both).
+void launch_preprocess_segs(PrepTable& t, int nseg, float pad_val, PrepSeg* table_dev, hipStream_t st);
 void launch_upsample8(const float* in, int in_cstride, int in_coff, int C, int N, int hl, int wl, int Hs, int Ws,
                       float* out, hipStream_t st);
 void launch_heat_full(const float* mid, int Cm, int coff, int P, int N, int Hs, int Ws, int H, int W, double sy,

@@ -53,6 +53,7 @@ SIGNATURES = {
     "opose_hand_forward": (_I, [_P, _P, _I, _I, _I, _P, _I]),
     "opose_hand_forward_pyramid": (_I, [_P, _I, C.POINTER(_P), _P, _P, _P, C.POINTER(_P), _I]),
     "opose_body_infer": (_I, [_P, _P, _I, _I, _I, _L, _L, C.POINTER(Params), _P, _I]),
+    "opose_body_infer_groups": (_I, [_P, _I, C.POINTER(_P), _P, _P, _P, _P, _P, C.POINTER(Params), C.POINTER(_P), _I]),
     "opose_body_post": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(Params), _P, _I]),
     "opose_body_scale_geom": (_I, [_I, _I, C.POINTER(Params), _I, _P]),
     "opose_body_scale_maps": (_I, [_P, _P, _I, _I, _I, _L, _L, C.POINTER(Params), _I, _P, _I]),
@@ -81,6 +82,7 @@ SIGNATURES = {
     "opose_profile_read": (_I, [_P, C.c_char_p, _S]),
     "opose_debug_conv": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "opose_debug_preprocess": (_I, [_P, _P, _I, _I, _D, _I, _P, _P]),
+    "opose_debug_preprocess_groups": (_I, [_P, _I, C.POINTER(_P), _P, _P, _P, _D, _I, C.POINTER(_P), _P]),
     "opose_debug_conv_time": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "opose_debug_conv_x6": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "opose_debug_conv_segs": (_I, [_P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P,
@@ -173,6 +175,15 @@ def frames_view(frames, what="frames"):
         if copied:
             raise ValueError("%s with strides %s cannot be made dense" % (what, tuple(st)))
         v = v.contiguous() if dev else np.ascontiguousarray(v)
+
+
+def groups_args(views):
+    """frames_view results of the groups of one opose_body_infer_groups call -> the call's
+    (n_groups, bgr, N, H, W, row_stride, frame_stride) as ctypes arrays."""
+    n = len(views)
+    return (n, (C.c_void_p * n)(*[v[1] for v in views]), (C.c_int * n)(*[v[2] for v in views]),
+            (C.c_int * n)(*[v[3] for v in views]), (C.c_int * n)(*[v[4] for v in views]),
+            (C.c_int64 * n)(*[v[5] for v in views]), (C.c_int64 * n)(*[v[6] for v in views]))
 
 
 class Handle:

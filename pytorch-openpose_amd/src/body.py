@@ -14,8 +14,9 @@ person assembly.  Only the fixed-size per-frame record crosses PCIe.
 
 Extras beyond the reference (defaults = reference values, src/body.py:25-31):
 scale_search, boxsize, stride, padValue, thre1, thre2, device; `Body.batch(frames)` runs
-a video batch through one launch sequence; `Body.infer_records` keeps inputs/outputs on
-the device (multi-GPU gather, benchmark).
+a video batch through one launch sequence; `Body.batch_mixed(frames)` / `Body.batch_groups`
+run frames of different sizes in one lockstep pass; `Body.infer_records` (and
+`Body.infer_records_groups`) keep inputs/outputs on the device (multi-GPU gather, benchmark).
 """
 from __future__ import annotations
 
@@ -57,6 +58,36 @@ class Body(object):
         frames, ptr, N, H, W, rs, fs, _ = _native.frames_view(np.asarray(frames))
         return self._records(N, lambda rec: lib.opose_body_infer(self.handle.h, ptr, N, H, W, rs, fs, self.params,
                                                                  rec, 0))
+
+    def groups_per_pass(self):
+        """Groups one opose_body_infer_groups call takes: every (group, scale) pair is a segment."""
+        return max(1, _native.MAX_SCALES // self.params.n_scales)
+
+    def batch_groups(self, groups):
+        """groups: a list of uint8 arrays [N_g, H_g, W_g, 3] (or lists of equally sized frames), every
+        group with its own size -> a list, one entry per group, of lists of (candidate, subset).
+
+        The groups' networks run in one lockstep pass (opose_body_infer_groups), groups_per_pass()
+        groups per call; a group's results are Body.batch(group)'s."""
+        views = [_native.frames_view(np.stack(g) if isinstance(g, (list, tuple)) else np.asarray(g)) for g in groups]
+        per, out = self.groups_per_pass(), []
+        for i in range(0, len(views), per):
+            out += self._records_groups(views[i:i + per])
+        return out
+
+    def batch_mixed(self, frames):
+        """frames: a list of uint8 [H, W, 3] frames of any sizes -> list of (candidate, subset) in the
+        frames' order.  Frames of one size form a group of batch_groups, the groups in the order
+        their sizes first appear."""
+        where = {}  # (H, W) -> indices into frames
+        for i, f in enumerate(frames):
+            where.setdefault(tuple(np.shape(f)[:2]), []).append(i)
+        results = self.batch_groups([[frames[i] for i in idx] for idx in where.values()])
+        out = [None] * len(frames)
+        for idx, res in zip(where.values(), results):
+            for i, r in zip(idx, res):
+                out[i] = r
+        return out
 
     def post(self, maps, pad, H, W):
         """Post-network path only (src/body.py:52-212) on one scale.
@@ -210,6 +241,28 @@ class Body(object):
             self.handle.signal_torch()
         return records_dev
 
+    def infer_records_groups(self, frames_dev_list, records_dev_list=None):
+        """batch_groups on the device: frames_dev_list[g] torch.uint8 cuda [N_g, H_g, W_g, 3]; returns a
+        list of torch.uint8 cuda [N_g, record_bytes] tensors (records_dev_list when given).
+
+        Asynchronous, ordered after torch's current stream, and the records are complete in that
+        stream's order on return, as infer_records (not pipelined).  groups_per_pass() groups per
+        opose_body_infer_groups call."""
+        import torch
+        views = [_native.frames_view(f) for f in frames_dev_list]
+        if records_dev_list is None:
+            rb = self.handle.record_bytes()
+            records_dev_list = [torch.empty((v[2], rb), dtype=torch.uint8, device=v[0].device) for v in views]
+        if len(records_dev_list) != len(views):
+            raise ValueError("expected one records tensor per group")
+        per = self.groups_per_pass()
+        for i in range(0, len(views), per):
+            n, ptrs, N, H, W, rs, fs = _native.groups_args(views[i:i + per])
+            recs = (ctypes.c_void_p * n)(*[r.data_ptr() for r in records_dev_list[i:i + per]])
+            self.handle.torch_call(lib.opose_body_infer_groups, n, ptrs, N, H, W, rs, fs, self.params, recs,
+                                   _native.DEVICE_IO)
+        return records_dev_list
+
     def decode_records(self, records):
         """uint8 [N, record_bytes] (numpy or torch) -> list of (candidate, subset)."""
         if hasattr(records, "cpu"):
@@ -276,6 +329,20 @@ class Body(object):
             if rc not in (_native.OPOSE_OK, _native.OPOSE_E_CAPACITY, _native.OPOSE_E_ASSEMBLY):
                 self.handle.check(rc)  # the two let through are per-frame statuses: _decode raises them
             return [self._decode(r) for r in rec]
+
+    def _records_groups(self, views):
+        """One opose_body_infer_groups call on the groups `views` (frames_view results) into host
+        records, repeated as _records repeats its call -> per group a list of (candidate, subset)."""
+        n, ptrs, N, H, W, rs, fs = _native.groups_args(views)
+        while True:
+            recs = [np.empty((v[2], self.handle.record_bytes()), np.uint8) for v in views]
+            rc = lib.opose_body_infer_groups(self.handle.h, n, ptrs, N, H, W, rs, fs, self.params,
+                                             (ctypes.c_void_p * n)(*[r.ctypes.data for r in recs]), 0)
+            if rc == _native.OPOSE_E_CAPACITY and self._grow():
+                continue
+            if rc not in (_native.OPOSE_OK, _native.OPOSE_E_CAPACITY, _native.OPOSE_E_ASSEMBLY):
+                self.handle.check(rc)
+            return [[self._decode(r) for r in rec] for rec in recs]
 
     def _decode(self, rec):
         status, cand, subset = _native.decode_record(rec, self.peaks_per_part, self.max_people)
