@@ -495,6 +495,22 @@ int opose_debug_limb_greedy(opose_t* h, const double* score, const int32_t* part
  * have for the kernel to stage them all at once; beyond, it stages limb by limb */
 int opose_debug_assemble(opose_t* h, void* records, const int32_t* part_cnt, const int32_t* conn_i,
                          const int32_t* conn_j, const double* conn_s, const int32_t* conn_cnt, int N, int* stage);
+/* The hand extraction kernels (srcmx/Batch_model.py:86-102, srcmx/Batch_motion_Estimation.py:44-58),
+ * each through the call opose_batch_hand_extract makes, on host arrays and synchronously.
+ * (hand_boxes needs no hook: opose_batch_hand_boxes takes the poses.)
+ *
+ * hand_crops on N frames and their boxes [N][2][4] (as opose_batch_hand_crops, with its checks of
+ * N, boxsize and the strides): both output forms -- x [2N][3][boxsize][boxsize] float32, the
+ * network input v / 255 - 0.5, and crops [2N][boxsize][boxsize][3] uint8; either may be NULL, not
+ * both -- and status [2N], OPOSE_E_SHAPE for a present box that is empty or leaves the frame, which
+ * does not make the call fail */
+int opose_debug_hand_crops(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                           int64_t frame_stride, const int32_t* boxes, int boxsize, float* x, uint8_t* crops,
+                           int32_t* status);
+/* hand_backmap: peaks [2N][21][3] (x, y in crop pixels, score; read only where found [2N][21] is
+ * not 0) and boxes [N][2][4] -> handmat [N][42][3] */
+int opose_debug_hand_backmap(opose_t* h, const double* peaks, const int32_t* found, const int32_t* boxes, int N,
+                             int boxsize, double* handmat);
 
 #ifdef __cplusplus
 }

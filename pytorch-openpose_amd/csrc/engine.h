@@ -329,6 +329,9 @@ void preprocess_segs(opose_ctx* h, PrepTable& t, int nseg, const opose_params& p
 BatchGeom batch_geom(const opose_params& p, int H, int W);
 void batch_preprocess(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
                       const BatchGeom& g, float* x, hipStream_t stream);
+bool extract_batch_ok(int N, int boxsize);
+void run_hand_crops(opose_ctx* h, const uint8_t* fd, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
+                    const int32_t* boxes_dev, int bs, float* x, uint8_t* crops, int32_t* status_dev);
 // engine_rccl.cpp
 const Rccl& rccl();
 void rccl_check(ncclResult_t r);

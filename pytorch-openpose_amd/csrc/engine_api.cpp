@@ -793,7 +793,7 @@ int opose_batch_hand_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, 
 // ---- fast-mode hand extraction (srcmx/Batch_model.py:55-104, srcmx/utilmx.py:267-327,
 // srcmx/Batch_motion_Estimation.py:19-65) -------------------------------------------------------
 // grid z runs over the 2N slots of a batch
-static bool extract_batch_ok(int N, int boxsize) { return N > 0 && N <= 32767 && boxsize > 0 && boxsize % 8 == 0; }
+bool opose::extract_batch_ok(int N, int boxsize) { return N > 0 && N <= 32767 && boxsize > 0 && boxsize % 8 == 0; }
 
 // n values of T on the device: the caller's pointer (in_device), or the copy of the host values in buf
 template <class T>
@@ -820,8 +820,9 @@ static void run_hand_boxes(opose_ctx* h, const double* motion_dev, int N, int H,
     h->prof_end(pe);
 }
 
-static void run_hand_crops(opose_ctx* h, const uint8_t* fd, int64_t frame_stride, int64_t row_stride, int N, int H,
-                           int W, const int32_t* boxes_dev, int bs, float* x, uint8_t* crops, int32_t* status_dev) {
+void opose::run_hand_crops(opose_ctx* h, const uint8_t* fd, int64_t frame_stride, int64_t row_stride, int N,
+                           int H, int W, const int32_t* boxes_dev, int bs, float* x, uint8_t* crops,
+                           int32_t* status_dev) {
     ProfEntry pe;
     h->prof_begin(pe, "hand_crops", 0, 2.0 * N * bs * bs * ((x ? 12.0 : 0.0) + (crops ? 3.0 : 0.0)));
     launch_hand_crops(fd, frame_stride, row_stride, N, H, W, boxes_dev, bs, x, crops, status_dev, h->stream);

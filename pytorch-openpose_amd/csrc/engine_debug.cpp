@@ -988,3 +988,52 @@ int opose_debug_assemble(opose_t* h, void* records, const int32_t* part_cnt, con
     });
     return OPOSE_OK;
 }
+
+// ---- the hand extraction kernels one at a time (tests/test_gpu_hand_stages.py): the calls
+// opose_batch_hand_extract makes, on host arrays.  (hand_boxes: opose_batch_hand_boxes.)
+int opose_debug_hand_crops(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                           int64_t frame_stride, const int32_t* boxes, int boxsize, float* x, uint8_t* crops,
+                           int32_t* status) {
+    if (!h || !bgr || !boxes || !status || (!x && !crops) || H <= 0 || W <= 0 || !extract_batch_ok(N, boxsize))
+        return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const size_t slots = (size_t)2 * N, nx = slots * 3 * boxsize * boxsize;
+        DevBuf bb, xb, cb, sb;
+        const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, 0);
+        const int32_t* bd = to_device(h, bb, boxes, slots * 4);
+        float* xd = x ? xb.ensure<float>(nx, h->stream) : nullptr;
+        uint8_t* cd = crops ? cb.ensure<uint8_t>(nx, h->stream) : nullptr;
+        int32_t* sd = sb.ensure<int32_t>(slots, h->stream);
+        if (xd) OPOSE_HIP_CHECK(hipMemsetAsync(xd, kDebugFill, nx * 4, h->stream));
+        if (cd) OPOSE_HIP_CHECK(hipMemsetAsync(cd, kDebugFill, nx, h->stream));
+        OPOSE_HIP_CHECK(hipMemsetAsync(sd, kDebugFill, slots * 4, h->stream));
+        run_hand_crops(h, fd, frame_stride, row_stride, N, H, W, bd, boxsize, xd, cd, sd);
+        if (xd) to_host(h, x, xd, nx);
+        if (cd) to_host(h, crops, cd, nx);
+        to_host(h, status, sd, slots);
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_debug_hand_backmap(opose_t* h, const double* peaks, const int32_t* found, const int32_t* boxes, int N,
+                             int boxsize, double* handmat) {
+    if (!h || !peaks || !found || !boxes || !handmat || !extract_batch_ok(N, boxsize)) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const size_t slots = (size_t)2 * N;
+        DevBuf pb, fb, bb, hb;
+        const double* pd = to_device(h, pb, peaks, slots * 63);
+        const int32_t* fd = to_device(h, fb, found, slots * 21);
+        const int32_t* bd = to_device(h, bb, boxes, slots * 4);
+        double* hm = hb.ensure<double>((size_t)N * 126, h->stream);
+        OPOSE_HIP_CHECK(hipMemsetAsync(hm, kDebugFill, (size_t)N * 126 * 8, h->stream));
+        launch_hand_backmap(pd, fd, bd, N, boxsize, hm, h->stream);
+        to_host(h, handmat, hm, (size_t)N * 126);
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    });
+    return OPOSE_OK;
+}

@@ -58,7 +58,8 @@ def test_null_handle_is_an_argument_error_everywhere():
     assert {"opose_debug_batch_preprocess", "opose_debug_batch_heat", "opose_debug_blur5_nms",
             "opose_debug_batch_hand_label", "opose_debug_conv_segs", "opose_debug_chain",
             "opose_debug_conv1", "opose_debug_peaks_finalize", "opose_debug_paf_score",
-            "opose_debug_limb_greedy", "opose_debug_assemble"} <= set(checked)
+            "opose_debug_limb_greedy", "opose_debug_assemble", "opose_debug_hand_crops",
+            "opose_debug_hand_backmap"} <= set(checked)
 
 
 def test_default_params_are_reference_constants():

@@ -14,6 +14,7 @@ import torch  # before libopose loads: the library then shares torch's HIP runti
 
 from conftest import GOLDEN
 from oracle import glue_standins
+from oracle.hand_extract import backmap
 
 pytestmark = pytest.mark.gpu
 
@@ -76,29 +77,10 @@ def test_crops_equal_the_reference_bytes(bh, scenes, boxsize, strided):
         assert np.array_equal(bh.crops(torch.from_numpy(scenes["full"]).cuda(), scenes["motion"], boxsize, ROI), ref)
 
 
-def _backmap(peaks, boxes, boxsize):
-    """The loop body of Batch_hand_extraction (srcmx/Batch_motion_Estimation.py:42-58) in numpy."""
-    out = np.zeros((len(boxes), 42, 3))
-    for n in range(len(boxes)):
-        r = np.array(peaks[2 * n + 1], dtype=np.float64)
-        rx, ry, rw = boxes[n, 1, :3].astype(np.float64)
-        r[:, :2] = r[:, :2] * rw / boxsize
-        r[:, 0] = np.where(r[:, 0] == 0, r[:, 0], r[:, 0] + rx)
-        r[:, 1] = np.where(r[:, 1] == 0, r[:, 1], r[:, 1] + ry)
-        out[n, 21:] = r
-        lft = np.array(peaks[2 * n], dtype=np.float64)
-        lx, ly, lw = boxes[n, 0, :3].astype(np.float64)
-        lft[:, :2] = lft[:, :2] * lw / boxsize
-        lft[:, 0] = np.where(lft[:, 0] == 0, lft[:, 0], lw - lft[:, 0] - 1 + lx)
-        lft[:, 1] = np.where(lft[:, 1] == 0, lft[:, 1], lft[:, 1] + ly)
-        out[n, :21] = lft
-    return out
-
-
 def test_extract_is_crops_then_batch_hand_then_backmap(bh, scenes, batch64):
     crops = bh.crops(scenes["full"], scenes["motion"], 64, ROI)
     peaks = bh(crops.reshape(10, 64, 64, 3))
-    ref = _backmap(peaks, bh.boxes(scenes["motion"], (H, W)), 64)
+    ref = backmap(peaks, None, bh.boxes(scenes["motion"], (H, W)), 64)  # (every row of peaks as it is)
     print("composition: parts found per hand", (ref[..., 2] != 0).reshape(5, 2, 21).sum(2).tolist())
     assert (ref[..., 2] != 0).any()  # not a comparison of zeros
     _same_handmat(batch64, ref)
