@@ -24,6 +24,9 @@
  *                                  Estimation.py:83-108      opose_body_records_pose (parity entry point)
  *   one scale of Body.__call__     src/body.py:36-50         opose_body_scale_maps; its output rows
  *                                                            opose_body_band_maps (C5 split)
+ *   util.draw_bodypose             src/util.py:44-77         opose_draw_records
+ *   DisplayPose's canvas           srcmx/MotionEstimation.py opose_draw_motion (draw_bodypose +
+ *                                  :281-295                  utilmx.draw_handpose_by_opencv)
  *
  * Conventions: plain pointers and sizes only; 0 = OK, negative = error (see opose_status).
  * Host pointers are caller-owned and read-only; the library copies them. A handle owns one
@@ -335,6 +338,41 @@ int opose_batch_body_extract(opose_t* h, const uint8_t* bgr, int N, int H, int W
                              int64_t frame_stride, const opose_params* p, double* pose, int32_t* status,
                              int flags);
 
+/* ---- drawing (src/util.py:44-77 draw_bodypose, srcmx/utilmx.py:212-227 draw_handpose_by_opencv,
+ * srcmx/MotionEstimation.py:281-295 DisplayPose) ------------------------------------------------ */
+/* Skeletons drawn over N frames bgr uint8 [H][W][3] (strides in bytes, as opose_body_infer; H, W <=
+ * 16384) into `out`: a dense [N][H][W][3] buffer, or bgr itself to draw in place.  Colours go to
+ * channels 0, 1, 2 in the order the reference lists them; every coordinate is truncated toward zero
+ * first, as the reference's int() does.  The covered pixels follow one rule, restated in NumPy by
+ * tests/draw_cases.py and equal to it bit for bit (OpenCV's own edge pixels are not restated):
+ *   disc  (cv2.circle, radius 4)      dx*dx + dy*dy <= 16 from the centre; opaque
+ *   limb  (ellipse2Poly + fillConvexPoly + addWeighted 0.4 / 0.6) about the reference's centre
+ *         (int(mean x), int(mean y)), with a = int(length / 2), (c, s) = cos / sin of int(angle)
+ *         whole degrees and A = a + 0.5, B = 4.5:  u = dx*c + dy*s, v = dy*c - dx*s, covered iff
+ *         u*u*(B*B) + v*v*(A*A) <= (A*A)*(B*B) in float64; a covered pixel becomes
+ *         rint(old * 0.4 + colour * 0.6), half to even; others keep their value
+ *   line  (cv2.line, thickness 2)     squared distance to the segment <= 1, in integers; opaque
+ * status [N] per frame: OPOSE_OK, or the frame is left as it was (in place: untouched; else copied)
+ * -- OPOSE_E_ARG when a coordinate that would be drawn is not finite or outside +-16384.  With
+ * OPOSE_IN_DEVICE the inputs (bgr and records / motion) are device memory; with OPOSE_OUT_DEVICE
+ * out and status are, and the call is asynchronous on the handle's stream and returns OPOSE_OK;
+ * else it returns the worst per-frame status.
+ *
+ * opose_draw_records: util.draw_bodypose(frame, candidate, subset) with each frame's Body record
+ * (read as opose_body_records_pose reads it, at the handle's current capacity; 8-byte aligned):
+ * discs part by part, then the first 17 limbs limb by limb, each over the people in subset order.
+ * A record whose own status is not OPOSE_OK draws nothing and hands that status on; a subset index
+ * the record does not hold is OPOSE_E_ARG. */
+int opose_draw_records(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                       int64_t frame_stride, const void* records, uint8_t* out, int32_t* status, int flags);
+/* DisplayPose's canvas for MotionMat rows motion [N][joints][3], joints 18 or 60: the row as one
+ * person (joint i absent iff its three values sum to 0), and with 60 joints the two hands of
+ * rows 18..38 and 39..59: per hand 20 edges between keypoints whose x + y is not 0, then a disc at
+ * every one of the 21 keypoints (a missing one draws at (0, 0), as in the reference). */
+int opose_draw_motion(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
+                      int64_t frame_stride, const double* motion, int joints, uint8_t* out, int32_t* status,
+                      int flags);
+
 /* Hand on N crops uint8 [H][W][3] (util.handDetect gives squares): peaks [N][21][3]
  * (x, y, score), found [N][21] (0 = part missing, the reference's [0,0,0] row). */
 int opose_hand_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
@@ -511,6 +549,17 @@ int opose_debug_hand_crops(opose_t* h, const uint8_t* bgr, int N, int H, int W, 
  * not 0) and boxes [N][2][4] -> handmat [N][42][3] */
 int opose_debug_hand_backmap(opose_t* h, const double* peaks, const int32_t* found, const int32_t* boxes, int N,
                              int boxsize, double* handmat);
+/* The drawing setup kernel alone (src/util.py:53-72 up to the cv2 calls: which primitives, in which
+ * order, with which integer parameters): src is N Body records at the handle's capacity (joints 0)
+ * or MotionMat rows [N][joints][3] (joints 18 / 60) for H x W frames -> prims [N][cap][12] int32
+ * with cap = 35 * max_people, 35 or 117 slots in draw order: kind (0 nothing, 1 disc, 2 limb, 3
+ * line), colour c0 | c1 << 8 | c2 << 16, centre x, y (a line's first end), a limb's a and its
+ * whole degrees mod 360 (a line's second end), the covering box x0, y0, x1, y1 cut to the frame
+ * (half open; empty: zeros), two zeros.  counts [N]: the frame's slots, or 0 when its status is
+ * not OPOSE_OK (its slots are then undefined); slots past the count are zero.  status [N] as
+ * opose_draw_records / opose_draw_motion. */
+int opose_debug_draw_prims(opose_t* h, const void* src, int N, int joints, int H, int W, int32_t* prims,
+                           int32_t* counts, int32_t* status);
 
 #ifdef __cplusplus
 }

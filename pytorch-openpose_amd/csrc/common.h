@@ -175,6 +175,15 @@ inline RecordLayout make_record_layout(int ppp, int maxp) {
     return r;
 }
 
+// int(v) of a subset entry as a candidate row of a record holding n_cand rows: -1 stays -1 (the
+// caller's "missing" / Python's last row), [0, n_cand) is itself, anything else (NaN included)
+// is kBadIndex.  Compared as float64 before the conversion, so no value overflows the int.
+constexpr int kBadIndex = -2;
+__device__ __forceinline__ int cand_index(double v, int n_cand) {
+    if (!(v > -2.0 && v < (double)n_cand)) return kBadIndex;
+    return (int)v;  // truncates toward zero, as int() does
+}
+
 // cubic-resize descriptor (OpenCV INTER_CUBIC, see imgproc.hip)
 struct ResizeAxis {
     int src, dst;     // sizes

@@ -330,6 +330,10 @@ BatchGeom batch_geom(const opose_params& p, int H, int W);
 void batch_preprocess(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
                       const BatchGeom& g, float* x, hipStream_t stream);
 bool extract_batch_ok(int N, int boxsize);
+bool draw_dims_ok(int N, int H, int W);
+int draw_cap(const opose_ctx* h, int joints);
+void run_draw_setup(opose_ctx* h, const uint8_t* rec_dev, const double* motion_dev, int joints, int N, int H, int W,
+                    int32_t* prims, int32_t* counts, int32_t* status_dev);
 void run_hand_crops(opose_ctx* h, const uint8_t* fd, int64_t frame_stride, int64_t row_stride, int N, int H, int W,
                     const int32_t* boxes_dev, int bs, float* x, uint8_t* crops, int32_t* status_dev);
 // engine_rccl.cpp
@@ -420,6 +424,9 @@ struct opose_ctx {
     // fast-mode body extraction (opose_body_records_pose / opose_batch_body_extract): staged poses
     // and per-frame status (the records are in `records`)
     opose::DevBuf px_pose, px_status;
+    // drawing (opose_draw_records / opose_draw_motion): the primitive tables, per-frame counts and
+    // status, staged poses, and the canvases of a call whose `out` is host memory
+    opose::DevBuf draw_prims, draw_counts, draw_status, draw_motion, draw_out;
     // opose_batch_hand_extract cuts its 2N crops into chunks the conv kernels can address (as
     // opose_hand_infer_crops does); OPOSE_EXTRACT_CHUNK=n at handle creation: n crops per chunk
     // instead (tests/test_gpu_hand_extract.py runs a small batch in two chunks)

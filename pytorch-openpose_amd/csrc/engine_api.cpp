@@ -1084,3 +1084,95 @@ int opose_hand_post(opose_t* h, const float* const* maps, const int* hl, const i
     return OPOSE_OK;
 }
 
+// ---- drawing (src/util.py:44-77, srcmx/utilmx.py:212-227, srcmx/MotionEstimation.py:281-295) ----
+// grid z runs over the frames; the coordinate bound of the pixel rule covers the frame size
+bool opose::draw_dims_ok(int N, int H, int W) {
+    return N > 0 && N <= 32767 && H > 0 && W > 0 && H <= 16384 && W <= 16384;
+}
+
+// primitive slots per frame: 18 discs + 17 limbs per person of a record at the handle's capacity
+// (joints 0) or of the one person of a MotionMat row, and 20 edges + 21 discs per hand
+int opose::draw_cap(const opose_ctx* h, int joints) { return joints == 0 ? 35 * h->maxp : (joints == 60 ? 117 : 35); }
+
+void opose::run_draw_setup(opose_ctx* h, const uint8_t* rec_dev, const double* motion_dev, int joints, int N, int H,
+                           int W, int32_t* prims, int32_t* counts, int32_t* status_dev) {
+    const int cap = draw_cap(h, joints);
+    ProfEntry pe;
+    h->prof_begin(pe, "draw_setup", 0, (double)N * cap * (kDrawPrimInts * 4 + 48));
+    launch_draw_setup(rec_dev, make_record_layout(h->ppp, h->maxp), motion_dev, joints, N, H, W, cap, prims, counts,
+                      status_dev, h->stream);
+    h->prof_end(pe);
+}
+
+// The two launches of a draw call on staged sources (device records, or device rows of `joints`
+// joints) and what surrounds them: the frames staged like every frame entry point's, the canvases
+// in the caller's device memory, or in the handle's and copied to the host.  out == bgr in one
+// memory space draws in place.  Every buffer is sized before anything is enqueued.
+static int run_draw(opose_ctx* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride, int64_t frame_stride,
+                    const uint8_t* rec_dev, const double* motion_dev, int joints, uint8_t* out, int32_t* status,
+                    int flags) {
+    const bool id = flags & OPOSE_IN_DEVICE, od = flags & OPOSE_OUT_DEVICE;
+    const bool inplace = out == bgr && id == od;
+    const int cap = draw_cap(h, joints);
+    const size_t dense = (size_t)N * H * W * 3;
+    int32_t* prims = h->draw_prims.ensure<int32_t>((size_t)N * cap * kDrawPrimInts, h->stream);
+    int32_t* counts = h->draw_counts.ensure<int32_t>((size_t)N, h->stream);
+    int32_t* sd = od ? status : h->draw_status.ensure<int32_t>((size_t)N, h->stream);
+    uint8_t* canvas = inplace ? nullptr : (od ? out : h->draw_out.ensure<uint8_t>(dense, h->stream));
+    const uint8_t* fd = stage_frames(h, bgr, N, H, W, row_stride, frame_stride, flags);
+    int64_t crs = (int64_t)W * 3, cfs = crs * H;
+    if (inplace) {  // the caller's device frames, or their staged copy
+        canvas = const_cast<uint8_t*>(fd);
+        crs = row_stride;
+        cfs = frame_stride;
+    }
+    run_draw_setup(h, rec_dev, motion_dev, joints, N, H, W, prims, counts, sd);
+    ProfEntry pe;
+    h->prof_begin(pe, "draw_pixels", 0, 2.0 * (double)dense);
+    launch_draw_pixels(fd, frame_stride, row_stride, canvas, cfs, crs, N, H, W, prims, counts, cap, h->stream);
+    h->prof_end(pe);
+    if (od) {
+        h->prof_drain();
+        return OPOSE_OK;
+    }
+    if (!inplace) {
+        OPOSE_HIP_CHECK(hipMemcpyAsync(out, canvas, dense, hipMemcpyDeviceToHost, h->stream));
+    } else if (frame_stride == row_stride * H) {  // rows only: the bytes between them are the caller's
+        OPOSE_HIP_CHECK(hipMemcpy2DAsync(out, row_stride, canvas, row_stride, (size_t)W * 3, (size_t)N * H,
+                                         hipMemcpyDeviceToHost, h->stream));
+    } else {
+        for (int n = 0; n < N; ++n)
+            OPOSE_HIP_CHECK(hipMemcpy2DAsync(out + (size_t)n * frame_stride, row_stride, canvas + (size_t)n * frame_stride,
+                                             row_stride, (size_t)W * 3, H, hipMemcpyDeviceToHost, h->stream));
+    }
+    const int worst = worst_slot_status(h, sd, N, status);
+    h->prof_drain();
+    if (worst != OPOSE_OK) h->err = "a frame's record carries a status, indexes past its candidates, or a coordinate is out of range";
+    return worst;
+}
+
+int opose_draw_records(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride, int64_t frame_stride,
+                       const void* records, uint8_t* out, int32_t* status, int flags) {
+    if (!h || !bgr || !records || !out || !status || !draw_dims_ok(N, H, W)) return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    if (reinterpret_cast<uintptr_t>(records) % 8) return OPOSE_E_ARG;  // float64 rows at offset 16
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const uint8_t* rd = stage_values(h, h->records, static_cast<const uint8_t*>(records),
+                                         make_record_layout(h->ppp, h->maxp).bytes * N, flags & OPOSE_IN_DEVICE);
+        return run_draw(h, bgr, N, H, W, row_stride, frame_stride, rd, nullptr, 0, out, status, flags);
+    });
+}
+
+int opose_draw_motion(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride, int64_t frame_stride,
+                      const double* motion, int joints, uint8_t* out, int32_t* status, int flags) {
+    if (!h || !bgr || !motion || !out || !status || !draw_dims_ok(N, H, W)) return OPOSE_E_ARG;
+    if (row_stride < (int64_t)W * 3 || frame_stride < row_stride * H) return OPOSE_E_ARG;
+    if (joints != 18 && joints != 60) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const double* md = stage_values(h, h->draw_motion, motion, (size_t)N * joints * 3, flags & OPOSE_IN_DEVICE);
+        return run_draw(h, bgr, N, H, W, row_stride, frame_stride, nullptr, md, joints, out, status, flags);
+    });
+}
+

@@ -1037,3 +1037,34 @@ int opose_debug_hand_backmap(opose_t* h, const double* peaks, const int32_t* fou
     });
     return OPOSE_OK;
 }
+
+// ---- the drawing setup kernel alone (tests/test_gpu_draw.py), through the call the draw entry
+// points make
+int opose_debug_draw_prims(opose_t* h, const void* src, int N, int joints, int H, int W, int32_t* prims,
+                           int32_t* counts, int32_t* status) {
+    if (!h || !src || !prims || !counts || !status || !draw_dims_ok(N, H, W)) return OPOSE_E_ARG;
+    if (joints != 0 && joints != 18 && joints != 60) return OPOSE_E_ARG;
+    if (joints == 0 && reinterpret_cast<uintptr_t>(src) % 8) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const size_t slots = (size_t)N * draw_cap(h, joints) * kDrawPrimInts;
+        DevBuf sb, pb, cb, tb;
+        const uint8_t* rd = nullptr;
+        const double* md = nullptr;
+        if (joints == 0)
+            rd = to_device(h, sb, static_cast<const uint8_t*>(src), make_record_layout(h->ppp, h->maxp).bytes * N);
+        else
+            md = to_device(h, sb, static_cast<const double*>(src), (size_t)N * joints * 3);
+        int32_t* pd = pb.ensure<int32_t>(slots, h->stream);
+        int32_t* cd = cb.ensure<int32_t>((size_t)N, h->stream);
+        int32_t* td = tb.ensure<int32_t>((size_t)N, h->stream);
+        OPOSE_HIP_CHECK(hipMemsetAsync(pd, 0, slots * 4, h->stream));  // slots past a frame's count stay zero
+        run_draw_setup(h, rd, md, joints, N, H, W, pd, cd, td);
+        to_host(h, prims, pd, slots);
+        to_host(h, counts, cd, (size_t)N);
+        to_host(h, status, td, (size_t)N);
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}

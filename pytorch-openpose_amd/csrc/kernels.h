@@ -162,6 +162,21 @@ void launch_hand_backmap(const double* peaks, const int32_t* found, const int32_
 void launch_pose_select(const uint8_t* records, int N, const RecordLayout& L, double* pose, int32_t* status,
                         hipStream_t st);
 
+// draw.hip: skeletons drawn into uint8 frames.  draw_setup writes per frame a table of `cap`
+// primitive slots of kDrawPrimInts int32 each, in draw order -- kind (0 none, 1 disc, 2 limb,
+// 3 line), colour (c0 | c1 << 8 | c2 << 16), centre x, y (a line's first end), two parameters (a
+// limb's semi-axis a and table degree, a line's second end), the box x0, y0, x1, y1 cut to the
+// frame (half open; empty: zeros), two zeros -- with the frame's slot count (0 unless its status is
+// OPOSE_OK) and status.  joints 0: the frames' Body records of layout L (cap 35 * L.max_people);
+// 18 / 60: MotionMat rows [N][joints][3] (cap 35 / 117).
+constexpr int kDrawPrimInts = 12;
+constexpr int kDrawThreads = 256, kDrawTileW = 32, kDrawTileH = 8;  // a workgroup's pixel tile
+void launch_draw_setup(const uint8_t* records, const RecordLayout& L, const double* motion, int joints, int N, int H,
+                       int W, int cap, int32_t* prims, int32_t* counts, int32_t* status, hipStream_t st);
+// src / dst: N frames [H][W][3] with frame / row strides in bytes; dst may be src (in place)
+void launch_draw_pixels(const uint8_t* src, int64_t sfs, int64_t srs, uint8_t* dst, int64_t dfs, int64_t drs, int N,
+                        int H, int W, const int32_t* prims, const int32_t* counts, int cap, hipStream_t st);
+
 // post.hip
 void launch_gauss_nms(const void* avg, bool f32, int NP, int H, int W, double thre, int cap, int* cnt, int* list,
                       double* list_score, hipStream_t st);

@@ -102,6 +102,9 @@ SIGNATURES = {
     "opose_debug_assemble": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "opose_debug_hand_crops": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _I, _P, _P, _P]),
     "opose_debug_hand_backmap": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "opose_draw_records": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _P, _P, _I]),
+    "opose_draw_motion": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _I, _P, _P, _I]),
+    "opose_debug_draw_prims": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
 }
 EXPORTED = list(SIGNATURES)
 

@@ -303,6 +303,103 @@ class Body(object):
         self._check_worst(rc, status)
         return pose, status
 
+    # ------------------------------------------------------------------ drawing
+    def draw_records_status(self, frames, records, out=None):
+        """util.draw_bodypose (src/util.py:44-77) of every frame's Body record, on the device
+        (opose_draw_records): frames uint8 [N, H, W, 3] (or one [H, W, 3]; a strided region of
+        interest is taken as it is) and records uint8 [N, record_bytes] at the handle's current
+        capacity -> (canvases, status int32 [N]).  out=None: new dense canvases; `out is frames`:
+        drawn in place; else a dense uint8 [N, H, W, 3] buffer.  numpy in gives numpy out; torch
+        CUDA frames and records give CUDA tensors with no synchronisation, complete in torch's
+        current-stream order.  A frame whose status is not 0 (its record's own status, or
+        OPOSE_E_ARG for an index past the candidates or a coordinate outside +-16384) is left as it
+        was.  The covered pixels follow the rule include/opose.h states, which util.draw_bodypose's
+        host rasteriser shares for the discs only."""
+        rb = self.handle.record_bytes()
+        dev = hasattr(records, "data_ptr") and records.is_cuda
+        if not dev:
+            records = np.ascontiguousarray(records.cpu().numpy() if hasattr(records, "cpu") else records)
+        else:
+            records = records.contiguous()
+        if str(records.dtype).split(".")[-1] != "uint8" or records.ndim != 2 or records.shape[1] != rb:
+            raise ValueError("expected uint8 records [N, %d]" % rb)
+        return self._draw(lib.opose_draw_records, frames, records, (), out)
+
+    def draw_motion_status(self, frames, motion, out=None):
+        """DisplayPose's canvas (srcmx/MotionEstimation.py:281-295) for MotionMat rows motion
+        [N, 18 | 60, 3] float64 over frames [N, H, W, 3], on the device (opose_draw_motion): the
+        row as one person through draw_bodypose, then with 60 joints both hands as
+        utilmx.draw_handpose_by_opencv draws them -> (canvases, status int32 [N]).  frames, out,
+        memory spaces and status as draw_records_status."""
+        dev = hasattr(motion, "data_ptr") and motion.is_cuda
+        if not dev:
+            motion = np.ascontiguousarray(motion.cpu().numpy() if hasattr(motion, "cpu") else motion, dtype=np.float64)
+        else:
+            motion = motion.contiguous()
+        if str(motion.dtype).split(".")[-1] != "float64" or motion.ndim != 3 or motion.shape[1] not in (18, 60) \
+                or motion.shape[2] != 3:
+            raise ValueError("expected float64 MotionMat rows [N, 18 | 60, 3]")
+        return self._draw(lib.opose_draw_motion, frames, motion, (int(motion.shape[1]),), out)
+
+    def draw_records(self, frames, records, out=None):
+        """draw_records_status's canvases; a frame's non-zero status raises what Body() raises for
+        it (reading the status of CUDA inputs waits for the call)."""
+        canvas, status = self.draw_records_status(frames, records, out)
+        self.raise_draw_status(status)
+        return canvas
+
+    def draw_motion(self, frames, motion, out=None):
+        """draw_motion_status's canvases; a frame's non-zero status raises (see draw_records)."""
+        canvas, status = self.draw_motion_status(frames, motion, out)
+        self.raise_draw_status(status)
+        return canvas
+
+    def raise_draw_status(self, status):
+        """The per-frame status [N] of a draw call as draw_records / draw_motion raise it (nothing
+        when all 0)."""
+        if hasattr(status, "cpu"):
+            status = status.cpu().numpy()
+        for s in status[status != 0]:
+            _native.raise_record_status(int(s), self.peaks_per_part, self.max_people)
+
+    def _draw(self, fn, frames, src, extra, out):
+        """fn(handle, frames..., src, *extra, out, status, flags) for frames / src / out in one
+        memory space -> (canvases shaped like frames, status)."""
+        batch = _as_batch(frames)
+        v, ptr, N, H, W, rs, fs, dev = _native.frames_view(batch)
+        if dev != bool(hasattr(src, "data_ptr") and src.is_cuda):
+            raise ValueError("frames and what is drawn must both be numpy arrays or both CUDA tensors")
+        if len(src) != N:
+            raise ValueError("expected one record or MotionMat row per frame: %d" % N)
+        if out is None:
+            if dev:
+                import torch
+                canvas = torch.empty((N, H, W, 3), dtype=torch.uint8, device=v.device)
+            else:
+                canvas = np.empty((N, H, W, 3), np.uint8)
+            optr = _native._ptr(canvas)
+        else:
+            canvas = _as_batch(out)
+            ov, optr, oN, oH, oW, ors, ofs, odev = _native.frames_view(canvas)
+            if (oN, oH, oW, odev) != (N, H, W, dev) or optr != _native._ptr(canvas):
+                raise ValueError("out must be uint8 [%d, %d, %d, 3] in the frames' memory space" % (N, H, W))
+            if optr == ptr and _native._ptr(batch) == ptr:
+                if (ors, ofs) != (rs, fs):
+                    raise ValueError("out overlaps the frames without being the frames")
+            elif (ors, ofs) != (3 * W, 3 * W * H):
+                raise ValueError("out must be dense, or the frames themselves to draw in place")
+        if dev:
+            import torch
+            status = torch.empty((N,), dtype=torch.int32, device=v.device)
+            self.handle.torch_call(fn, ptr, N, H, W, rs, fs, src.data_ptr(), *extra, optr, status.data_ptr(),
+                                   _native.DEVICE_IO)
+        else:
+            status = np.zeros((N,), np.int32)
+            rc = fn(self.handle.h, ptr, N, H, W, rs, fs, src.ctypes.data, *extra, optr, status.ctypes.data, 0)
+            self._check_worst(rc, status)
+        single = batch is not frames and getattr(frames, "ndim", 4) == 3
+        return (canvas[0] if single and out is None else (out if out is not None else canvas)), status
+
     # ------------------------------------------------------------------ helpers
     def _check_worst(self, rc, status):
         """rc of a call that returns its worst per-frame status, `status` zeroed before the call: a

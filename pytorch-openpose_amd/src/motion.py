@@ -296,7 +296,7 @@ def Batch_body_extraction(videopath, outpath, batch_size, recpoint, *, body, cap
     return _fast_mode_pass(videopath, outpath, batch_size, capture, 18, lambda frames: body.extract(frames, recpoint))
 
 
-def Batch_motion_extraction(videopath, outpath, batch_size, recpoint, *, body, hand, capture=None):
+def Batch_motion_extraction(videopath, outpath, batch_size, recpoint, *, body, hand, capture=None, render=None):
     """Both fast-mode passes of the reference (Batch_body_extraction, then Batch_hand_extraction
     on its poses, srcmx/Batch_motion_Estimation.py:19-113) in one pass over the video: MotionMat
     [T, 60, 3], body rows 0-17, left hand 18-38, right hand 39-59, written like
@@ -305,26 +305,63 @@ def Batch_motion_extraction(videopath, outpath, batch_size, recpoint, *, body, h
     the statuses come back in one download each; the two handles are ordered through torch's
     current stream.  A batch in which a frame overflows the body record capacity runs again
     through Batch_body.extract, which grows the capacity; other statuses raise what
-    Batch_body.extract / Batch_hand.extract raise."""
+    Batch_body.extract / Batch_hand.extract raise.
+
+    render: an optional callable that receives each batch's canvases, the frames cut to recpoint
+    with their rows drawn over them (Body.draw_motion; what the reference shows frame by frame with
+    DisplayPose) as a CUDA uint8 tensor [n, H, W, 3]: drawn on the device from the [n, 60, 3]
+    tensor the hand pass just produced, before anything is downloaded.  None: nothing changes."""
     import torch
     from . import _native
+    from .batch_model import _frames_view
     devc = torch.device("cuda", body.handle.device)
 
     def rows_of(frames):
         dev = torch.from_numpy(frames).to(devc)
         pose, bstat = body.extract_device(dev, recpoint)
         handmat, hstat = hand.extract_device(dev, pose, 368, recpoint)
-        rows = torch.cat([pose, handmat], 1).cpu().numpy()
+        rows_dev = torch.cat([pose, handmat], 1)
+        if render is not None:
+            view = _frames_view(dev, recpoint)[0]  # the region of interest as a strided view
+            canvases, dstat = body.draw_motion_status(view, rows_dev)
+        rows = rows_dev.cpu().numpy()
         bstat, hstat = bstat.cpu().numpy(), hstat.cpu().numpy()
         if (bstat == _native.OPOSE_E_CAPACITY).any():
             pose = body.extract(dev, recpoint)
-            return np.concatenate([pose, hand.extract(dev, pose, 368, recpoint)], 1)
+            rows = np.concatenate([pose, hand.extract(dev, pose, 368, recpoint)], 1)
+            if render is not None:
+                render(body.draw_motion(view, torch.from_numpy(rows).to(devc)))
+            return rows
         for s in bstat:
             _native.raise_record_status(int(s), body.peaks_per_part, body.max_people)
         hand.raise_status(hstat)
+        if render is not None:
+            body.raise_draw_status(dstat)
+            render(canvases)
         return rows
 
     return _fast_mode_pass(videopath, outpath, batch_size, capture, 60, rows_of)
+
+
+def Checkout_motion_data(frames, motion, recpoint=None, batch=32, *, body):
+    """The reference's check of an extraction run (Checkout_motion_data / DisplayPose,
+    srcmx/MotionEstimation.py:219-304) without its window: a generator of rendered uint8 batches
+    [n, H, W, 3], frame k cut to recpoint [(x0, y0), (x1, y1)] with row k of the MotionMat motion
+    [T, 18 | 60, 3] drawn over it (Body.draw_motion: body, and with 60 joints the hands), `batch`
+    frames at a time, in order, until the frames run out.  The reference shows each with
+    cv2.imshow; show, write or compare what this yields.  frames: any iterable of uint8 BGR frames
+    (a VideoFrames); when it reports a length other than T, the reference's line is printed.  More
+    frames than rows raise IndexError, as PoseMat[index] does there."""
+    motion = np.asarray(motion, dtype=np.float64)
+    if hasattr(frames, "__len__") and len(frames) != motion.shape[0]:
+        print('the count number is not equal')
+    index = 0
+    for b in _batches(frames, recpoint, batch):
+        n = len(b)
+        if index + n > len(motion):
+            raise IndexError("index %d is out of bounds for axis 0 with size %d" % (len(motion), len(motion)))
+        yield body.draw_motion(np.stack([np.ascontiguousarray(f) for f in b]), motion[index:index + n])
+        index += n
 
 
 def Extract_MotionData_from_Video(videopath, outpath, Recpoint, mode="body", overwrite=False, *, body, hand=None,

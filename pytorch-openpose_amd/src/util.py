@@ -6,11 +6,16 @@
 * npmax               src/util.py:205-210 (first row-major argmax)
 * draw_bodypose       src/util.py:44-77   (keypoint discs + translucent limb ellipses)
 * draw_handpose       src/util.py:80-113  (matplotlib hand skeleton)
-The drawing helpers are host-side rendering of the results, not part of the GPU
-path.  OpenCV is absent here, so draw_bodypose rasterises the reference's cv2.circle /
+The drawing helpers here are host-side rendering of the results on numpy canvases.
+OpenCV is absent here, so draw_bodypose rasterises the reference's cv2.circle /
 cv2.ellipse2Poly / cv2.fillConvexPoly / cv2.addWeighted calls itself (pixel parity with OpenCV
 unpinned); draw_handpose uses matplotlib as the reference does (its FigureCanvas.tostring_rgb
 is gone from this image's matplotlib 3.10, so the RGB buffer is read through buffer_rgba).
+The device path is Body.draw_records / Body.draw_motion (opose_draw_records / opose_draw_motion,
+csrc/draw.hip): whole frame batches, with a pixel rule that is stated exactly (include/opose.h,
+tests/draw_cases.py).  Its discs are draw_bodypose's bit for bit; its limb edges differ from
+draw_bodypose's, whose polygon fill (matplotlib's contains_points with a radius) has no statable
+edge rule (the measured share of differing limb pixels).
 """
 from __future__ import annotations
 
@@ -124,7 +129,8 @@ def _fill_convex(canvas, poly, color):
 
 def draw_bodypose(canvas, candidate, subset):
     """Keypoint discs (radius 4) drawn into `canvas` in place, then each of the first 17 limbs as
-    a filled ellipse (stick width 4) blended 0.4 canvas / 0.6 limb; returns the final canvas."""
+    a filled ellipse (stick width 4) blended 0.4 canvas / 0.6 limb; returns the final canvas.
+    On the device, for frame batches: Body.draw_records (same discs; its limb edges differ)."""
     stickwidth = 4
     for i in range(18):
         for n in range(len(subset)):
