@@ -27,6 +27,11 @@
  *   util.draw_bodypose             src/util.py:44-77         opose_draw_records
  *   DisplayPose's canvas           srcmx/MotionEstimation.py opose_draw_motion (draw_bodypose +
  *                                  :281-295                  utilmx.draw_handpose_by_opencv)
+ *   MotionJointFeatures            srcmx/PreprocessingData   opose_motion_features
+ *                                  .py:16-125
+ *   SlidingDistance(_torch)        srcmx/utilmx.py:330-372   opose_sliding_distance
+ *   ShapeletMatrixModel.train      srcmx/shapeletmodel.py:   opose_shapelet_find;
+ *                                  97-209                    opose_shapelet_mindist (first stage)
  *
  * Conventions: plain pointers and sizes only; 0 = OK, negative = error (see opose_status).
  * Host pointers are caller-owned and read-only; the library copies them. A handle owns one
@@ -373,6 +378,68 @@ int opose_draw_motion(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64
                       int64_t frame_stride, const double* motion, int joints, uint8_t* out, int32_t* status,
                       int flags);
 
+/* ---- shapelet search over motion data (srcmx/PreprocessingData.py:16-125 MotionJointFeatures,
+ * srcmx/utilmx.py:330-391 SlidingDistance / matrixprofile_torch, srcmx/shapeletmodel.py:93-209
+ * ShapeletMatrixModel.train) -------------------------------------------------------------------- */
+/* A ragged batch: seq float32 [L][D] row-major, n_seq sequences one after another (host memory, or
+ * device memory with OPOSE_IN_DEVICE); off int64 [n_seq + 1], always host memory, off[0] = 0,
+ * non-decreasing, off[n_seq] = L.  For a window of m rows sequence j has P_j = len_j - m + 1
+ * positions.  off, m, D and every P_j >= 1 are checked before anything is launched: OPOSE_E_SHAPE
+ * for a sequence shorter than m or a limit exceeded (m <= 128, D <= 1024, n_seq <= 4096, L < 2^31),
+ * OPOSE_E_ARG otherwise.  With OPOSE_OUT_DEVICE the outputs are device memory and the call is
+ * asynchronous on the handle's stream.
+ *
+ * The distance rule, all fp32, round to nearest, no fused multiply-add:
+ *   e(a, b) = sum over d = 0 .. D-1 ascending of (x[a][d] - y[b][d])^2, starting from +0
+ *   s(r, c) = sum over k = 0 .. m-1 ascending of e(r + k, c + k), starting from +0
+ *   dist    = sqrt(s), correctly rounded
+ * and a minimum over c is the first minimum of s (strict <, c ascending).  tests/shapelet_cases.py
+ * states it in NumPy; the results equal that statement bit for bit.  (The reference fills its
+ * distance matrix by the recurrence sqrt(prev^2 + new - old), which drifts: not reproduced.) */
+
+/* MotionJointFeatures: MotionMat rows motion float64 [L][joints][3], joints 18 or 60, ragged by off
+ * (len_j >= 0, L >= 1) -> out float32 [L][F][2], F = 6 (18 joints) or 46.  x, y are cast to float32
+ * first; the score never reaches the output.  featuremode 0, 1: a zero takes the last non-zero
+ * value at or before its row within its sequence (a leading zero stays); 2: a zero takes the first
+ * non-zero of rows r-1, r+1, r-2, r+2 of its sequence, from the unfilled data.  Body joints 2..7
+ * relative to joint 1, each hand's joints 1..20 relative to its joint 0 (rows 18, 39); in mode 2 a
+ * zero coordinate of a non-origin joint (the nose included) is the origin's first.  Modes 1, 2:
+ * divided by (nose.y - neck.y) + 1e-5f of the filled body group. */
+int opose_motion_features(opose_t* h, const double* motion, const int64_t* off, int n_seq, int joints,
+                          int featuremode, float* out, int flags);
+
+/* SlidingDistance of one pattern [m][D] (device memory with OPOSE_IN_DEVICE, as seq) against every
+ * sequence: dist float32, ragged, P_j values per sequence (sequence j's start at off[j] - j (m - 1)). */
+int opose_sliding_distance(opose_t* h, const float* pattern, int m, const float* seq, const int64_t* off,
+                           int n_seq, int D, float* dist, int flags);
+
+/* The first stage of the search.  Candidates: every start r of the sequences cand_seqs[0 ..
+ * n_cand_seqs) (host memory), rows ordered by (position in cand_seqs, r): n_cand = sum of their P_i.
+ * min2 float32 [n_cand][n_seq] = min over c of s(r, c) against sequence j (the squared distance),
+ * loc int32 [n_cand][n_seq] its first c. */
+int opose_shapelet_mindist(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int m,
+                           const int32_t* cand_seqs, int n_cand_seqs, float* min2, int32_t* loc, int flags);
+
+/* The whole search (ShapeletMatrixModel.train).  labels uint8 [n_labels] (host memory, 0 / 1, at
+ * least one 1); n_seq is n_labels, or 2 * n_labels with sequence k + n_labels the mirrored copy of
+ * k.  Candidates: the starts of the sequences i < n_labels with label 1, i ascending then r
+ * ascending, processed in chunks of at most max_cands (0: the library's default) so the workspace
+ * is bounded; the running winner stays on the device.  Per candidate, with s_k the smaller s of
+ * sample k's pair (the original on a tie; unmirrored: its own):
+ *   order   the samples by (bits of s_k, k) ascending
+ *   num     max over t = 0 .. n_labels of negs + (positives - negatives among the first t), negs
+ *           the number of zero labels; the reference's score is num / n_labels
+ *   loss    the float64 sum, k ascending, of (double) sqrt(s_k) over the positive samples' own
+ *           (unmirrored) values, divided by their count
+ * and a candidate replaces the best only with a larger num, or an equal num and a smaller loss.
+ * best int32 [4]: the winner's sequence (shapeindex), its start, its num, candidates scored;
+ * best_loss float64 [1]; dis float32 [n_seq] and locs int32 [n_seq]: the winner's distances and
+ * locations against every sequence.  cand_num int32 / cand_loss float64 [candidates]: every
+ * candidate's num and loss, or both NULL. */
+int opose_shapelet_find(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int m,
+                        const uint8_t* labels, int n_labels, int max_cands, int32_t* best, double* best_loss,
+                        float* dis, int32_t* locs, int32_t* cand_num, double* cand_loss, int flags);
+
 /* Hand on N crops uint8 [H][W][3] (util.handDetect gives squares): peaks [N][21][3]
  * (x, y, score), found [N][21] (0 = part missing, the reference's [0,0,0] row). */
 int opose_hand_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
@@ -560,6 +627,11 @@ int opose_debug_hand_backmap(opose_t* h, const double* peaks, const int32_t* fou
  * opose_draw_records / opose_draw_motion. */
 int opose_debug_draw_prims(opose_t* h, const void* src, int N, int joints, int H, int W, int32_t* prims,
                            int32_t* counts, int32_t* status);
+/* Stages two and three of opose_shapelet_find on given host arrays: min2 [n_cand][n_seq] and labels
+ * [n_labels] -> every row's num [n_cand] and loss [n_cand], and the selection: winner int32 [4] = 0,
+ * the winning row, its num, n_cand; win_loss its loss. */
+int opose_debug_shapelet_score(opose_t* h, const float* min2, int n_cand, int n_seq, const uint8_t* labels,
+                               int n_labels, int32_t* num, double* loss, int32_t* winner, double* win_loss);
 
 #ifdef __cplusplus
 }

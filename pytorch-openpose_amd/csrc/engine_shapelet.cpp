@@ -1,0 +1,324 @@
+// engine_shapelet.cpp — the shapelet search entry points: validation of the ragged batch, the block
+// table of the candidate starts, chunking, and the launches of shapelet.hip.
+#include "engine.h"
+
+namespace opose {
+
+// The ragged batch of a window call: off[0] = 0, non-decreasing, every sequence at least m rows, all
+// within the limits of shapelet.h.  Nothing is launched unless this returns OPOSE_OK.
+static int shp_check(opose_ctx* h, const int64_t* off, int n_seq, int D, int m) {
+    if (n_seq < 1 || D < 1 || m < 1 || off[0] != 0) {
+        h->err = "shapelet: n_seq, D and m must be positive and off[0] must be 0";
+        return OPOSE_E_ARG;
+    }
+    if (n_seq > kShpMaxSeq || D > kShpMaxD || m > kShpMaxM) {
+        h->err = "shapelet: n_seq, D or m beyond the supported limit";
+        return OPOSE_E_SHAPE;
+    }
+    for (int j = 0; j < n_seq; ++j)
+        if (off[j + 1] < off[j]) {
+            h->err = "shapelet: off must not decrease";
+            return OPOSE_E_ARG;
+        }
+    if (off[n_seq] > kShpMaxRows) {
+        h->err = "shapelet: too many rows";
+        return OPOSE_E_SHAPE;
+    }
+    for (int j = 0; j < n_seq; ++j)
+        if (off[j + 1] - off[j] < m) {
+            h->err = "shapelet: a sequence is shorter than the window";
+            return OPOSE_E_SHAPE;
+        }
+    return OPOSE_OK;
+}
+
+// The candidate starts of the sequences `cands` (in the order given, r ascending) as table entries
+// of at most kShpTR starts, grouped into chunks of at most `cap` candidates; an entry's out0 counts
+// from its chunk's first candidate.  chunks: per chunk {first entry, entries, candidates}.
+struct ShpChunk {
+    int b0, nb, nc;
+};
+static int64_t shp_table(const int64_t* off, int m, const std::vector<int>& cands, int64_t cap,
+                         std::vector<ShpBlock>& blocks, std::vector<ShpChunk>& chunks) {
+    int64_t total = 0;
+    ShpChunk cur{0, 0, 0};
+    for (int i : cands) {
+        const int P = (int)(off[i + 1] - off[i]) - m + 1;
+        for (int r = 0; r < P;) {
+            if (cur.nc == cap) {
+                chunks.push_back(cur);
+                cur = ShpChunk{(int)blocks.size(), 0, 0};
+            }
+            const int n = (int)std::min<int64_t>(std::min(kShpTR, P - r), cap - cur.nc);
+            blocks.push_back(ShpBlock{i, r, n, cur.nc});
+            cur.nb++;
+            cur.nc += n;
+            r += n;
+            total += n;
+        }
+    }
+    if (cur.nc) chunks.push_back(cur);
+    return total;
+}
+
+template <class T>
+static const T* shp_stage(opose_ctx* h, DevBuf& buf, const T* v, size_t n, bool in_device) {
+    if (in_device) return v;
+    T* d = buf.ensure<T>(n, h->stream);
+    OPOSE_HIP_CHECK(hipMemcpyAsync(d, v, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    return d;
+}
+
+// a host table the call built itself: on the device before the table goes out of scope
+template <class T>
+static const T* shp_upload(opose_ctx* h, DevBuf& buf, const std::vector<T>& v) {
+    T* d = buf.ensure<T>(v.size(), h->stream);
+    OPOSE_HIP_CHECK(hipMemcpyAsync(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    return d;
+}
+
+static void run_mindist(opose_ctx* h, const float* seq, const int64_t* off, int n_seq, int D, int m,
+                        const ShpBlock* blocks, int nb, int nc, int64_t L, float* min2, int32_t* loc) {
+    ProfEntry pe;
+    h->prof_begin(pe, "shapelet_mindist", 3.0 * nc * (double)(L - (int64_t)n_seq * (m - 1)) * D, 8.0 * nc * n_seq);
+    launch_shapelet_mindist(seq, off, n_seq, D, m, blocks, nb, min2, loc, h->stream);
+    h->prof_end(pe);
+}
+
+static void run_score(opose_ctx* h, const float* min2, int nc, int n_seq, int n_labels, const uint8_t* labels, int negs,
+                      int32_t* num, double* loss) {
+    ProfEntry pe;
+    h->prof_begin(pe, "shapelet_score", 0, 4.0 * nc * n_seq);
+    launch_shapelet_score(min2, nc, n_seq, n_labels, labels, negs, num, loss, h->stream);
+    h->prof_end(pe);
+}
+
+static void run_select(opose_ctx* h, const int32_t* num, const double* loss, int nc, const ShpBlock* blocks, int nb,
+                       const float* min2, const int32_t* loc, int n_seq, int first, int32_t* best, double* best_loss,
+                       float* dis, int32_t* locs) {
+    ProfEntry pe;
+    h->prof_begin(pe, "shapelet_select", 0, 12.0 * nc);
+    launch_shapelet_select(num, loss, nc, blocks, nb, min2, loc, n_seq, first, best, best_loss, dis, locs, h->stream);
+    h->prof_end(pe);
+}
+
+// labels: n_labels values 0 / 1 for n_seq = n_labels or 2 * n_labels sequences; negs: the zeros
+static int shp_labels_check(opose_ctx* h, const uint8_t* labels, int n_labels, int n_seq, int* negs) {
+    if (n_labels < 1 || (n_seq != n_labels && n_seq != 2 * (int64_t)n_labels)) {
+        h->err = "shapelet: n_seq must be n_labels or 2 * n_labels";
+        return OPOSE_E_ARG;
+    }
+    if (n_labels > kShpMaxSeq) {
+        h->err = "shapelet: too many labels";
+        return OPOSE_E_SHAPE;
+    }
+    *negs = 0;
+    for (int k = 0; k < n_labels; ++k) {
+        if (labels[k] > 1) {
+            h->err = "shapelet: labels must be 0 or 1";
+            return OPOSE_E_ARG;
+        }
+        *negs += labels[k] == 0;
+    }
+    return OPOSE_OK;
+}
+
+// the winner block the select kernel writes when the outputs are host memory:
+// int32 best[4] | double best_loss | float dis[n_seq] | int32 locs[n_seq]
+static size_t shp_best_bytes(int n_seq) { return 24 + 8 * (size_t)n_seq; }
+
+}  // namespace opose
+
+using namespace opose;
+
+int opose_motion_features(opose_t* h, const double* motion, const int64_t* off, int n_seq, int joints, int featuremode,
+                          float* out, int flags) {
+    if (!h || !motion || !off || !out || n_seq < 1) return OPOSE_E_ARG;
+    if ((joints != 18 && joints != 60) || featuremode < 0 || featuremode > 2 || off[0] != 0) return OPOSE_E_ARG;
+    for (int j = 0; j < n_seq; ++j)
+        if (off[j + 1] < off[j]) return OPOSE_E_ARG;
+    const int64_t L = off[n_seq];
+    if (L < 1) return OPOSE_E_ARG;
+    if (L > kShpMaxRows) return OPOSE_E_SHAPE;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const bool od = flags & OPOSE_OUT_DEVICE;
+        const int F = joints == 18 ? 6 : 46;
+        const size_t nblocks = (size_t)((L + kFeatRows - 1) / kFeatRows);
+        const double* md = shp_stage(h, h->shp_in, motion, (size_t)L * joints * 3, flags & OPOSE_IN_DEVICE);
+        const int64_t* offd = shp_stage(h, h->shp_off, off, (size_t)n_seq + 1, false);
+        int32_t* carry = h->shp_carry.ensure<int32_t>(nblocks * 2 * joints, h->stream);
+        float* outd = od ? out : h->shp_out.ensure<float>((size_t)L * F * 2, h->stream);
+        ProfEntry pe;
+        h->prof_begin(pe, "motion_features", 0, (double)L * (joints * 24.0 + F * 8.0));
+        launch_motion_features(md, L, joints, offd, n_seq, featuremode, carry, outd, h->stream);
+        h->prof_end(pe);
+        if (!od) {
+            OPOSE_HIP_CHECK(hipMemcpyAsync(out, outd, (size_t)L * F * 8, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_sliding_distance(opose_t* h, const float* pattern, int m, const float* seq, const int64_t* off, int n_seq,
+                           int D, float* dist, int flags) {
+    if (!h || !pattern || !seq || !off || !dist) return OPOSE_E_ARG;
+    if (const int rc = shp_check(h, off, n_seq, D, m)) return rc;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const bool id = flags & OPOSE_IN_DEVICE, od = flags & OPOSE_OUT_DEVICE;
+        const int64_t L = off[n_seq];
+        const size_t n_out = (size_t)(L - (int64_t)n_seq * (m - 1));
+        const float* sd = shp_stage(h, h->shp_seq, seq, (size_t)L * D, id);
+        const float* pd = shp_stage(h, h->shp_in, pattern, (size_t)m * D, id);
+        const int64_t* offd = shp_stage(h, h->shp_off, off, (size_t)n_seq + 1, false);
+        float* outd = od ? dist : h->shp_out.ensure<float>(n_out, h->stream);
+        ProfEntry pe;
+        h->prof_begin(pe, "sliding_distance", 3.0 * n_out * m * D, 4.0 * n_out * m * D);
+        launch_sliding_distance(pd, m, sd, offd, n_seq, D, L, outd, h->stream);
+        h->prof_end(pe);
+        if (!od) {
+            OPOSE_HIP_CHECK(hipMemcpyAsync(dist, outd, n_out * 4, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_shapelet_mindist(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int m,
+                           const int32_t* cand_seqs, int n_cand_seqs, float* min2, int32_t* loc, int flags) {
+    if (!h || !seq || !off || !cand_seqs || !min2 || !loc || n_cand_seqs < 1) return OPOSE_E_ARG;
+    if (const int rc = shp_check(h, off, n_seq, D, m)) return rc;
+    for (int i = 0; i < n_cand_seqs; ++i)
+        if (cand_seqs[i] < 0 || cand_seqs[i] >= n_seq) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const bool od = flags & OPOSE_OUT_DEVICE;
+        const int64_t L = off[n_seq];
+        std::vector<ShpBlock> blocks;
+        std::vector<ShpChunk> chunks;
+        const std::vector<int> cands(cand_seqs, cand_seqs + n_cand_seqs);
+        const int64_t nc = shp_table(off, m, cands, INT32_MAX, blocks, chunks);
+        if (nc > INT32_MAX) throw std::invalid_argument("shapelet: too many candidates for one call");
+        const size_t n_out = (size_t)nc * n_seq;
+        const float* sd = shp_stage(h, h->shp_seq, seq, (size_t)L * D, flags & OPOSE_IN_DEVICE);
+        const int64_t* offd = shp_stage(h, h->shp_off, off, (size_t)n_seq + 1, false);
+        float* md = od ? min2 : h->shp_min2.ensure<float>(n_out, h->stream);
+        int32_t* ld = od ? loc : h->shp_loc.ensure<int32_t>(n_out, h->stream);
+        const ShpBlock* bd = shp_upload(h, h->shp_blocks, blocks);
+        run_mindist(h, sd, offd, n_seq, D, m, bd, (int)blocks.size(), (int)nc, L, md, ld);
+        if (!od) {
+            OPOSE_HIP_CHECK(hipMemcpyAsync(min2, md, n_out * 4, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(loc, ld, n_out * 4, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_debug_shapelet_score(opose_t* h, const float* min2, int n_cand, int n_seq, const uint8_t* labels,
+                               int n_labels, int32_t* num, double* loss, int32_t* winner, double* win_loss) {
+    if (!h || !min2 || !labels || !num || !loss || !winner || !win_loss || n_cand < 1) return OPOSE_E_ARG;
+    int negs = 0;
+    if (const int rc = shp_labels_check(h, labels, n_labels, n_seq, &negs)) return rc;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        DevBuf mb, lb, yb, nb, sb, bb, tb;
+        const size_t n = (size_t)n_cand * n_seq;
+        float* md = mb.ensure<float>(n, h->stream);
+        int32_t* ld = lb.ensure<int32_t>(n, h->stream);
+        uint8_t* yd = yb.ensure<uint8_t>((size_t)n_labels, h->stream);
+        int32_t* nd = nb.ensure<int32_t>((size_t)n_cand, h->stream);
+        double* sd = sb.ensure<double>((size_t)n_cand, h->stream);
+        uint8_t* best = bb.ensure<uint8_t>(shp_best_bytes(n_seq), h->stream);
+        OPOSE_HIP_CHECK(hipMemcpyAsync(md, min2, n * 4, hipMemcpyHostToDevice, h->stream));
+        OPOSE_HIP_CHECK(hipMemsetAsync(ld, 0, n * 4, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(yd, labels, (size_t)n_labels, hipMemcpyHostToDevice, h->stream));
+        // one table entry for all rows: the winner's "start" is its row
+        const std::vector<ShpBlock> one{ShpBlock{0, 0, n_cand, 0}};
+        const ShpBlock* bd = shp_upload(h, tb, one);
+        run_score(h, md, n_cand, n_seq, n_labels, yd, negs, nd, sd);
+        run_select(h, nd, sd, n_cand, bd, 1, md, ld, n_seq, 1, reinterpret_cast<int32_t*>(best),
+                   reinterpret_cast<double*>(best + 16), reinterpret_cast<float*>(best + 24),
+                   reinterpret_cast<int32_t*>(best + 24 + 4 * (size_t)n_seq));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(num, nd, (size_t)n_cand * 4, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(loss, sd, (size_t)n_cand * 8, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(winner, best, 16, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(win_loss, best + 16, 8, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_shapelet_find(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int m,
+                        const uint8_t* labels, int n_labels, int max_cands, int32_t* best, double* best_loss,
+                        float* dis, int32_t* locs, int32_t* cand_num, double* cand_loss, int flags) {
+    if (!h || !seq || !off || !labels || !best || !best_loss || !dis || !locs) return OPOSE_E_ARG;
+    if (max_cands < 0 || (cand_num == nullptr) != (cand_loss == nullptr)) return OPOSE_E_ARG;
+    int negs = 0;
+    if (const int rc = shp_labels_check(h, labels, n_labels, n_seq, &negs)) return rc;
+    if (negs == n_labels) {
+        h->err = "shapelet: no positive sequence, so no candidate";
+        return OPOSE_E_ARG;
+    }
+    if (const int rc = shp_check(h, off, n_seq, D, m)) return rc;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const bool od = flags & OPOSE_OUT_DEVICE;
+        const int64_t L = off[n_seq];
+        std::vector<int> cands;
+        for (int i = 0; i < n_labels; ++i)
+            if (labels[i]) cands.push_back(i);
+        std::vector<ShpBlock> blocks;
+        std::vector<ShpChunk> chunks;
+        const int64_t total = shp_table(off, m, cands, max_cands ? max_cands : kShpDefaultCands, blocks, chunks);
+        if (total > INT32_MAX) throw std::invalid_argument("shapelet: too many candidates for one call");
+        int cap = 0;
+        for (const ShpChunk& c : chunks) cap = std::max(cap, c.nc);
+        const float* sd = shp_stage(h, h->shp_seq, seq, (size_t)L * D, flags & OPOSE_IN_DEVICE);
+        const int64_t* offd = shp_stage(h, h->shp_off, off, (size_t)n_seq + 1, false);
+        const uint8_t* yd = shp_stage(h, h->shp_labels, labels, (size_t)n_labels, false);
+        float* md = h->shp_min2.ensure<float>((size_t)cap * n_seq, h->stream);
+        int32_t* ld = h->shp_loc.ensure<int32_t>((size_t)cap * n_seq, h->stream);
+        // every candidate's num / loss when asked for, else one chunk's
+        const bool all = cand_num != nullptr;
+        int32_t* nd = all && od ? cand_num : h->shp_num.ensure<int32_t>(all ? (size_t)total : (size_t)cap, h->stream);
+        double* sl = all && od ? cand_loss : h->shp_loss.ensure<double>(all ? (size_t)total : (size_t)cap, h->stream);
+        uint8_t* wb = od ? nullptr : h->shp_best.ensure<uint8_t>(shp_best_bytes(n_seq), h->stream);
+        int32_t* bestd = od ? best : reinterpret_cast<int32_t*>(wb);
+        double* blossd = od ? best_loss : reinterpret_cast<double*>(wb + 16);
+        float* disd = od ? dis : reinterpret_cast<float*>(wb + 24);
+        int32_t* locsd = od ? locs : reinterpret_cast<int32_t*>(wb + 24 + 4 * (size_t)n_seq);
+        const ShpBlock* bd = shp_upload(h, h->shp_blocks, blocks);
+        size_t done = 0;
+        for (size_t ci = 0; ci < chunks.size(); ++ci) {
+            const ShpChunk& c = chunks[ci];
+            int32_t* cn = nd + (all ? done : 0);
+            double* cl = sl + (all ? done : 0);
+            run_mindist(h, sd, offd, n_seq, D, m, bd + c.b0, c.nb, c.nc, L, md, ld);
+            run_score(h, md, c.nc, n_seq, n_labels, yd, negs, cn, cl);
+            run_select(h, cn, cl, c.nc, bd + c.b0, c.nb, md, ld, n_seq, ci == 0, bestd, blossd, disd, locsd);
+            done += (size_t)c.nc;
+        }
+        if (!od) {
+            OPOSE_HIP_CHECK(hipMemcpyAsync(best, wb, 16, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(best_loss, wb + 16, 8, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(dis, wb + 24, 4 * (size_t)n_seq, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(locs, wb + 24 + 4 * (size_t)n_seq, 4 * (size_t)n_seq, hipMemcpyDeviceToHost,
+                                           h->stream));
+            if (all) {
+                OPOSE_HIP_CHECK(hipMemcpyAsync(cand_num, nd, (size_t)total * 4, hipMemcpyDeviceToHost, h->stream));
+                OPOSE_HIP_CHECK(hipMemcpyAsync(cand_loss, sl, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream));
+            }
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}

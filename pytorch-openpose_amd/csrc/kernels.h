@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "common.h"
+#include "shapelet.h"
 #include "x6_pack.h"
 
 namespace opose {
@@ -176,6 +177,22 @@ void launch_draw_setup(const uint8_t* records, const RecordLayout& L, const doub
 // src / dst: N frames [H][W][3] with frame / row strides in bytes; dst may be src (in place)
 void launch_draw_pixels(const uint8_t* src, int64_t sfs, int64_t srs, uint8_t* dst, int64_t dfs, int64_t drs, int N,
                         int H, int W, const int32_t* prims, const int32_t* counts, int cap, hipStream_t st);
+
+// shapelet.hip: shapelet search over motion data (limits, tile constants and ShpBlock: shapelet.h).
+// off [n_seq + 1] is the ragged batch's row offsets on the device; carry: nblocks x 2 * joints int32
+// of workspace (nblocks = fill blocks of kFeatRows rows)
+void launch_motion_features(const double* motion, int64_t L, int joints, const int64_t* off, int n_seq, int mode,
+                            int32_t* carry, float* out, hipStream_t st);
+void launch_sliding_distance(const float* pat, int m, const float* seq, const int64_t* off, int n_seq, int D, int64_t L,
+                             float* dist, hipStream_t st);
+// min2 / loc [rows][n_seq]: table entry b writes rows out0 .. out0 + nvalid - 1
+void launch_shapelet_mindist(const float* seq, const int64_t* off, int n_seq, int D, int m, const ShpBlock* blocks,
+                             int n_blocks, float* min2, int32_t* loc, hipStream_t st);
+void launch_shapelet_score(const float* min2, int n_cand, int n_seq, int n_labels, const uint8_t* labels, int negs,
+                           int32_t* num, double* loss, hipStream_t st);
+void launch_shapelet_select(const int32_t* num, const double* loss, int n_cand, const ShpBlock* blocks, int n_blocks,
+                            const float* min2, const int32_t* loc, int n_seq, int first, int32_t* best,
+                            double* best_loss, float* dis, int32_t* locs, hipStream_t st);
 
 // post.hip
 void launch_gauss_nms(const void* avg, bool f32, int NP, int H, int W, double thre, int cap, int* cnt, int* list,

@@ -1,0 +1,32 @@
+// shapelet.h — limits and tile constants of the shapelet search (shapelet.hip, engine_shapelet.cpp).
+// tests/test_gpu_shapelet.py parses the constants below, so its edge lengths follow the code.
+#pragma once
+#include <cstdint>
+
+namespace opose {
+
+// limits: beyond them the entry points answer OPOSE_E_SHAPE
+constexpr int kShpMaxM = 128;      // window length
+constexpr int kShpMaxD = 1024;     // feature columns
+constexpr int kShpMaxSeq = 4096;   // sequences of a ragged batch (grid y; the score kernel's LDS keys)
+constexpr int64_t kShpMaxRows = 2147483647;  // L, rows of a ragged batch (int32 row indices)
+// shapelet_mindist: a workgroup takes kShpTR candidate starts of one sequence against one target and
+// walks the target's positions kShpTC at a time, streaming D through LDS kShpDC columns at a time
+constexpr int kShpTR = 32;
+constexpr int kShpTC = 32;
+constexpr int kShpDC = 16;
+constexpr int kShpThreads = 256;
+constexpr int kShpSub = kShpThreads / kShpTR;  // threads sharing one candidate start's positions
+// opose_shapelet_find: candidates per chunk when the caller passes max_cands = 0
+constexpr int kShpDefaultCands = 2048;
+// motion_features: rows per fill block (the carry of the forward fill crosses these)
+constexpr int kFeatRows = 64;
+constexpr int kFeatThreads = 256;
+
+// kShpTR consecutive candidate starts r0 .. r0 + nvalid - 1 of sequence `seq`; out0: the row of the
+// launch's output that start r0 writes
+struct ShpBlock {
+    int32_t seq, r0, nvalid, out0;
+};
+
+}  // namespace opose

@@ -1,0 +1,429 @@
+// shapelet.hip — shapelet search over motion data: MotionMat rows to joint features, the sliding
+// distance of a window against ragged sequences, and the selection of the window that separates
+// the labels best.
+//
+// Reference steps replaced (hitmaxiang/pytorch-openpose):
+//  * srcmx/PreprocessingData.py:16-125   MotionJointFeatures (ProcessingTheNonValue,
+//    CorrespondingValue, the nose-neck scale)        => feat_blocklast, feat_carry, feat_compute
+//  * srcmx/utilmx.py:330-372             SlidingDistance(_torch)          => sliding_distance
+//  * srcmx/utilmx.py:375-391 + srcmx/shapeletmodel.py:140-152  matrixprofile_torch and the
+//    per-sample torch.min                                                 => shapelet_mindist
+//  * srcmx/shapeletmodel.py:157-209      Bipartition_score, the loss and the best-candidate update
+//                                                                         => shapelet_score, shapelet_select
+//
+// The distance rule (fp32, one rounding per operation; this file is built without FMA contraction):
+//   e(a, b) = sum over d ascending of (x[a,d] - y[b,d])^2, from +0
+//   s(r, c) = sum over k ascending of e(r+k, c+k), from +0;  dist = sqrt(s)
+// and a minimum over c is the first minimum of s.  s is never negative, so its bit pattern as an
+// unsigned integer orders like its value.  The reference's running recurrence (add the new term,
+// subtract the old) is not used: every s is the direct sum.
+//
+// Every address below derives from the validated integers of the call (off, m, D, the block table
+// the host builds from them), never from a data value.
+#include "common.h"
+#include "kernels.h"
+#include "shapelet.h"
+
+namespace opose {
+
+// the sequence a global row belongs to: the last j < n_seq with off[j] <= g (sequences may be empty)
+__device__ inline int seq_of_row(const int64_t* __restrict__ off, int n_seq, int64_t g) {
+    int lo = 0, hi = n_seq;  // off[lo] <= g < off[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= g)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// ------------------------------------------------------------------------------------ features
+// x or y of a joint, as float32: column c = 2 * joint + (0: x, 1: y) of a row of `joints` joints
+__device__ inline float feat_load(const double* __restrict__ motion, int64_t row, int joints, int c) {
+    return (float)motion[(row * joints + (c >> 1)) * 3 + (c & 1)];
+}
+
+// last[b][c]: the last row of fill block b whose column c is not zero, -1: none
+__global__ __launch_bounds__(kFeatThreads) void feat_blocklast(const double* __restrict__ motion, int64_t L, int joints,
+                                                               int nblocks, int32_t* __restrict__ last) {
+    const int C = 2 * joints;
+    const int64_t i = (int64_t)blockIdx.x * kFeatThreads + threadIdx.x;
+    if (i >= (int64_t)nblocks * C) return;
+    const int b = (int)(i / C), c = (int)(i % C);
+    const int64_t r0 = (int64_t)b * kFeatRows;
+    const int64_t r1 = min(r0 + kFeatRows, L);
+    int32_t res = -1;
+    for (int64_t r = r1 - 1; r >= r0; --r)
+        if (feat_load(motion, r, joints, c) != 0.0f) {
+            res = (int32_t)r;
+            break;
+        }
+    last[i] = res;
+}
+
+// in place, per column: last[b][c] becomes the last non-zero row of the blocks before b (the carry)
+__global__ __launch_bounds__(kFeatThreads) void feat_carry(int32_t* __restrict__ last, int nblocks, int C) {
+    const int c = blockIdx.x * kFeatThreads + threadIdx.x;
+    if (c >= C) return;
+    int32_t run = -1;
+    for (int b = 0; b < nblocks; ++b) {
+        const int32_t own = last[(size_t)b * C + c];
+        last[(size_t)b * C + c] = run;
+        if (own >= 0) run = own;
+    }
+}
+
+// One workgroup per fill block.  The block's filled x / y values go to LDS (modes 0, 1: a thread per
+// column walks the block's rows from the carry, and a carry from before the row's own sequence does
+// not count; mode 2: the first non-zero of rows r-1, r+1, r-2, r+2 of the sequence), then every
+// output of the block is formed from them.  out [L][F][2], F = 6 or 46.
+__global__ __launch_bounds__(kFeatThreads) void feat_compute(const double* __restrict__ motion, int64_t L, int joints,
+                                                             const int64_t* __restrict__ off, int n_seq, int mode,
+                                                             const int32_t* __restrict__ carry,
+                                                             float* __restrict__ out) {
+    __shared__ float vals[kFeatRows][120];
+    __shared__ int64_t row_lo[kFeatRows], row_hi[kFeatRows];
+    const int C = 2 * joints, t = threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * kFeatRows;
+    const int rows = (int)min((int64_t)kFeatRows, L - r0);
+    if (t < rows) {
+        const int j = seq_of_row(off, n_seq, r0 + t);
+        row_lo[t] = off[j];
+        row_hi[t] = off[j + 1];
+    }
+    __syncthreads();
+    if (mode == 2) {
+        for (int i = t; i < rows * C; i += kFeatThreads) {
+            const int r = i / C, c = i % C;
+            const int64_t g = r0 + r;
+            float v = feat_load(motion, g, joints, c);
+            if (v == 0.0f) {
+                for (int s = 1; s <= 2; ++s) {
+                    float u = 0.0f;
+                    if (g - s >= row_lo[r]) u = feat_load(motion, g - s, joints, c);
+                    if (u == 0.0f && g + s < row_hi[r]) u = feat_load(motion, g + s, joints, c);
+                    if (u != 0.0f) {
+                        v = u;
+                        break;
+                    }
+                }
+            }
+            vals[r][c] = v;
+        }
+    } else if (t < C) {
+        int64_t last = carry[(size_t)blockIdx.x * C + t];
+        float lastv = last >= 0 ? feat_load(motion, last, joints, t) : 0.0f;
+        for (int r = 0; r < rows; ++r) {
+            float v = feat_load(motion, r0 + r, joints, t);
+            if (v != 0.0f) {
+                last = r0 + r;
+                lastv = v;
+            } else if (last >= row_lo[r]) {
+                v = lastv;
+            }
+            vals[r][t] = v;
+        }
+    }
+    __syncthreads();
+    const int F = joints == 18 ? 6 : 46;
+    for (int i = t; i < rows * F * 2; i += kFeatThreads) {
+        const int r = i / (2 * F), f = (i >> 1) % F, k = i & 1;
+        int joint, origin;
+        if (f < 6) {
+            joint = 2 + f;
+            origin = 1;
+        } else if (f < 26) {
+            joint = 19 + (f - 6);
+            origin = 18;
+        } else {
+            joint = 40 + (f - 26);
+            origin = 39;
+        }
+        float vj = vals[r][2 * joint + k];
+        const float vo = vals[r][2 * origin + k];
+        if (mode == 2 && vj == 0.0f) vj = vo;
+        float v = vj - vo;
+        if (mode >= 1) {
+            float nose = vals[r][1];
+            const float neck = vals[r][3];
+            if (mode == 2 && nose == 0.0f) nose = neck;
+            const float scale = (nose - neck) + 1e-5f;
+            v = v / scale;
+        }
+        out[((r0 + r) * F + f) * 2 + k] = v;
+    }
+}
+
+void launch_motion_features(const double* motion, int64_t L, int joints, const int64_t* off, int n_seq, int mode,
+                            int32_t* carry, float* out, hipStream_t st) {
+    const int nblocks = (int)((L + kFeatRows - 1) / kFeatRows);
+    const int C = 2 * joints;
+    if (mode != 2) {
+        const int64_t n = (int64_t)nblocks * C;
+        hipLaunchKernelGGL(feat_blocklast, dim3((unsigned)((n + kFeatThreads - 1) / kFeatThreads)), dim3(kFeatThreads), 0,
+                           st, motion, L, joints, nblocks, carry);
+        hipLaunchKernelGGL(feat_carry, dim3((C + kFeatThreads - 1) / kFeatThreads), dim3(kFeatThreads), 0, st, carry,
+                           nblocks, C);
+    }
+    hipLaunchKernelGGL(feat_compute, dim3(nblocks), dim3(kFeatThreads), 0, st, motion, L, joints, off, n_seq, mode, carry,
+                       out);
+}
+
+// ------------------------------------------------------------------------------------ profile mode
+// One thread per row of the batch: position c of its sequence, when the sequence has one there.
+// dist is ragged, P_j values per sequence: sequence j starts at off[j] - j * (m - 1).
+__global__ __launch_bounds__(kShpThreads) void sliding_distance(const float* __restrict__ pat, int m,
+                                                                const float* __restrict__ seq,
+                                                                const int64_t* __restrict__ off, int n_seq, int D,
+                                                                float* __restrict__ dist) {
+    const int64_t g = (int64_t)blockIdx.x * kShpThreads + threadIdx.x;
+    if (g >= off[n_seq]) return;
+    const int j = seq_of_row(off, n_seq, g);
+    if (g + m > off[j + 1]) return;  // fewer than m rows left in the sequence
+    float acc = 0.0f;
+    for (int k = 0; k < m; ++k) {
+        const float* x = pat + (size_t)k * D;
+        const float* y = seq + (g + k) * D;
+        float e = 0.0f;
+        for (int d = 0; d < D; ++d) {
+            const float t = x[d] - y[d];
+            e = e + t * t;
+        }
+        acc = acc + e;
+    }
+    dist[g - (int64_t)j * (m - 1)] = sqrtf(acc);
+}
+
+void launch_sliding_distance(const float* pat, int m, const float* seq, const int64_t* off, int n_seq, int D, int64_t L,
+                             float* dist, hipStream_t st) {
+    hipLaunchKernelGGL(sliding_distance, dim3((unsigned)((L + kShpThreads - 1) / kShpThreads)), dim3(kShpThreads), 0, st,
+                       pat, m, seq, off, n_seq, D, dist);
+}
+
+// ------------------------------------------------------------------------------------ mindist mode
+// Workgroup (block table entry, target sequence j): min over c of s(r, c) and its first c, for the
+// entry's candidate starts r.  Per block of kShpTC target positions:
+//   1. E[a][q] = e(a, a + q - (kShpTR - 1)) for the rows a of the candidate window rows and the
+//      diagonals q that the tile's outputs use -- a band, not the square -- accumulated in LDS while
+//      D streams through the staging tiles xs / ys in chunks of kShpDC, d ascending;
+//   2. s(r, c) = E[r][q] + E[r+1][q] + ... along its diagonal, k ascending, against the running
+//      (min, loc) that a thread keeps in registers for its positions c = sub, sub + kShpSub, ...
+// Position blocks ascend, so a strict < keeps a thread's first minimum; the kShpSub partial results
+// of a start are merged on (bits, loc).  No atomics: a result does not depend on scheduling.
+constexpr int kShpNA = kShpTR + kShpMaxM - 1;  // candidate rows a workgroup may touch
+constexpr int kShpNB = kShpTC + kShpMaxM - 1;  // target rows of one position block
+constexpr int kShpND = kShpTR + kShpTC - 1;    // diagonals of a tile
+static_assert(kShpThreads == kShpTR * kShpSub, "threads = starts x sub-positions");
+static_assert((kShpNA * kShpND + (kShpNA + kShpNB) * (kShpDC + 1)) * 4 <= 65536, "static LDS");
+
+__global__ __launch_bounds__(kShpThreads) void shapelet_mindist(const float* __restrict__ seq,
+                                                                const int64_t* __restrict__ off, int n_seq, int D, int m,
+                                                                const ShpBlock* __restrict__ blocks,
+                                                                float* __restrict__ min2, int32_t* __restrict__ loc) {
+    __shared__ float E[kShpNA * kShpND];
+    __shared__ float xs[kShpNA * (kShpDC + 1)];
+    __shared__ float ys[kShpNB * (kShpDC + 1)];
+    const int t = threadIdx.x, j = blockIdx.y;
+    const ShpBlock blk = blocks[blockIdx.x];
+    const int64_t xo = off[blk.seq] + blk.r0;  // the window rows of the entry's starts: xo .. xo + xrows - 1
+    const int xrows = blk.nvalid + m - 1;
+    const int64_t yo = off[j];
+    const int ylen = (int)(off[j + 1] - yo), P = ylen - m + 1;
+    const int na = kShpTR + m - 1, nb = kShpTC + m - 1, nent = na * kShpND;
+    const int r = t / kShpSub, sub = t % kShpSub;
+    uint32_t best = 0xffffffffu;
+    int bloc = 0;
+    for (int c0 = 0; c0 < P; c0 += kShpTC) {
+        for (int e = t; e < nent; e += kShpThreads) E[e] = 0.0f;
+        for (int d0 = 0; d0 < D; d0 += kShpDC) {
+            const int dc = min(kShpDC, D - d0);
+            __syncthreads();  // the previous chunk's readers are done
+            for (int i = t; i < na * kShpDC; i += kShpThreads) {
+                const int a = i / kShpDC, d = i % kShpDC;
+                xs[a * (kShpDC + 1) + d] = (a < xrows && d < dc) ? seq[(xo + a) * D + d0 + d] : 0.0f;
+            }
+            for (int i = t; i < nb * kShpDC; i += kShpThreads) {
+                const int b = i / kShpDC, d = i % kShpDC;
+                ys[b * (kShpDC + 1) + d] = (c0 + b < ylen && d < dc) ? seq[(yo + c0 + b) * D + d0 + d] : 0.0f;
+            }
+            __syncthreads();
+            for (int e = t; e < nent; e += kShpThreads) {  // an entry stays with its thread
+                const int a = e / kShpND, b = a + e % kShpND - (kShpTR - 1);
+                if (a >= xrows || b < 0 || b >= nb || c0 + b >= ylen) continue;  // no output reads it
+                const float* x = xs + a * (kShpDC + 1);
+                const float* y = ys + b * (kShpDC + 1);
+                float acc = E[e];
+                for (int d = 0; d < dc; ++d) {
+                    const float v = x[d] - y[d];
+                    acc = acc + v * v;
+                }
+                E[e] = acc;
+            }
+        }
+        __syncthreads();
+        if (r < blk.nvalid) {
+            for (int c = sub; c < kShpTC && c0 + c < P; c += kShpSub) {
+                const float* diag = E + r * kShpND + (c - r + kShpTR - 1);
+                float acc = 0.0f;
+                for (int k = 0; k < m; ++k) acc = acc + diag[k * kShpND];
+                const uint32_t bits = __float_as_uint(acc);
+                if (bits < best) {
+                    best = bits;
+                    bloc = c0 + c;
+                }
+            }
+        }
+        __syncthreads();  // E is zeroed next
+    }
+    uint32_t* pb = reinterpret_cast<uint32_t*>(xs);
+    int* pl = reinterpret_cast<int*>(ys);
+    pb[t] = best;
+    pl[t] = bloc;
+    __syncthreads();
+    if (sub == 0 && r < blk.nvalid) {
+        for (int s = 1; s < kShpSub; ++s) {
+            const uint32_t ob = pb[t + s];
+            const int ol = pl[t + s];
+            if (ob < best || (ob == best && ol < bloc)) {
+                best = ob;
+                bloc = ol;
+            }
+        }
+        const size_t o = (size_t)(blk.out0 + r) * n_seq + j;
+        min2[o] = __uint_as_float(best);
+        loc[o] = bloc;
+    }
+}
+
+void launch_shapelet_mindist(const float* seq, const int64_t* off, int n_seq, int D, int m, const ShpBlock* blocks,
+                             int n_blocks, float* min2, int32_t* loc, hipStream_t st) {
+    hipLaunchKernelGGL(shapelet_mindist, dim3(n_blocks, n_seq), dim3(kShpThreads), 0, st, seq, off, n_seq, D, m, blocks,
+                       min2, loc);
+}
+
+// ------------------------------------------------------------------------------------ score
+// One workgroup per candidate row of min2 [n_cand][n_seq].  n_seq is n_labels, or 2 * n_labels with
+// sequence k + n_labels the mirrored copy of k: sample k's key is then the smaller s of the pair,
+// the original on a tie.  The samples are ordered by (bits of s, k) through a rank count, and
+//   num  = max over t = 0 .. n_labels of negs + (positives - negatives among the first t)
+//   loss = float64 sum, k ascending, of (double) sqrt(s_k) over the positive samples' own
+//          (unmirrored) values, divided by their count.
+__global__ __launch_bounds__(kShpThreads) void shapelet_score(const float* __restrict__ min2, int n_seq, int n_labels,
+                                                              const uint8_t* __restrict__ labels, int negs,
+                                                              int32_t* __restrict__ num, double* __restrict__ loss) {
+    __shared__ uint32_t key[kShpMaxSeq];
+    __shared__ uint8_t sorted[kShpMaxSeq];
+    const int t = threadIdx.x;
+    const float* row = min2 + (size_t)blockIdx.x * n_seq;
+    for (int k = t; k < n_labels; k += kShpThreads) {
+        uint32_t b = __float_as_uint(row[k]);
+        if (n_seq == 2 * n_labels) {
+            const uint32_t b2 = __float_as_uint(row[k + n_labels]);
+            if (b2 < b) b = b2;
+        }
+        key[k] = b;
+    }
+    __syncthreads();
+    for (int k = t; k < n_labels; k += kShpThreads) {
+        const uint32_t mine = key[k];
+        int rank = 0;
+        for (int o = 0; o < n_labels; ++o) {
+            const uint32_t v = key[o];
+            rank += (v < mine || (v == mine && o < k)) ? 1 : 0;
+        }
+        sorted[rank] = labels[k];
+    }
+    __syncthreads();
+    if (t == 0) {
+        int correct = negs, mx = negs;
+        for (int i = 0; i < n_labels; ++i) {
+            correct += sorted[i] ? 1 : -1;
+            mx = max(mx, correct);
+        }
+        num[blockIdx.x] = mx;
+    } else if (t == 64) {  // a second wave: the loss does not wait for the prefix walk
+        double acc = 0.0;
+        for (int k = 0; k < n_labels; ++k)
+            if (labels[k]) acc = acc + (double)sqrtf(row[k]);
+        loss[blockIdx.x] = acc / (double)(n_labels - negs);
+    }
+}
+
+void launch_shapelet_score(const float* min2, int n_cand, int n_seq, int n_labels, const uint8_t* labels, int negs,
+                           int32_t* num, double* loss, hipStream_t st) {
+    hipLaunchKernelGGL(shapelet_score, dim3(n_cand), dim3(kShpThreads), 0, st, min2, n_seq, n_labels, labels, negs, num,
+                       loss);
+}
+
+// ------------------------------------------------------------------------------------ selection
+// One workgroup.  The best of a chunk's n_cand candidates under (num larger, then loss smaller, then
+// the earlier candidate) against the running winner kept in best / best_loss, which a later
+// candidate replaces only when it is strictly better: the first candidate wins a full tie.
+//   best int32[4]: the winner's sequence, its start in that sequence, its num, candidates scored
+// A new winner's row of min2 / loc becomes dis (square roots) and locs.  first: no winner yet.
+struct ShpPick {
+    int num, q;
+    double loss;
+};
+__device__ inline bool shp_better(const ShpPick& a, const ShpPick& b) {
+    if (a.num != b.num) return a.num > b.num;
+    if (a.loss != b.loss) return a.loss < b.loss;
+    return a.q < b.q;
+}
+
+__global__ __launch_bounds__(kShpThreads) void shapelet_select(const int32_t* __restrict__ num,
+                                                               const double* __restrict__ loss, int n_cand,
+                                                               const ShpBlock* __restrict__ blocks, int n_blocks,
+                                                               const float* __restrict__ min2,
+                                                               const int32_t* __restrict__ loc, int n_seq, int first,
+                                                               int32_t* __restrict__ best, double* __restrict__ best_loss,
+                                                               float* __restrict__ dis, int32_t* __restrict__ locs) {
+    __shared__ ShpPick pick[kShpThreads];
+    __shared__ int winner;
+    const int t = threadIdx.x;
+    ShpPick p{-2, 0x7fffffff, 0.0};
+    for (int q = t; q < n_cand; q += kShpThreads) {
+        const ShpPick c{num[q], q, loss[q]};
+        if (shp_better(c, p)) p = c;
+    }
+    pick[t] = p;
+    __syncthreads();
+    for (int s = kShpThreads / 2; s > 0; s >>= 1) {
+        if (t < s && shp_better(pick[t + s], pick[t])) pick[t] = pick[t + s];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const ShpPick w = pick[0];
+        const int scored = first ? 0 : best[3];
+        const bool take = first || w.num > best[2] || (w.num == best[2] && w.loss < *best_loss);
+        winner = take ? w.q : -1;
+        if (take) {
+            int bi = 0;  // the table entry that holds output row w.q
+            for (int i = 0; i < n_blocks; ++i)
+                if (blocks[i].out0 <= w.q) bi = i;
+            best[0] = blocks[bi].seq;
+            best[1] = blocks[bi].r0 + (w.q - blocks[bi].out0);
+            best[2] = w.num;
+            *best_loss = w.loss;
+        }
+        best[3] = scored + n_cand;
+    }
+    __syncthreads();
+    const int w = winner;
+    if (w < 0) return;
+    for (int k = t; k < n_seq; k += kShpThreads) {
+        dis[k] = sqrtf(min2[(size_t)w * n_seq + k]);
+        locs[k] = loc[(size_t)w * n_seq + k];
+    }
+}
+
+void launch_shapelet_select(const int32_t* num, const double* loss, int n_cand, const ShpBlock* blocks, int n_blocks,
+                            const float* min2, const int32_t* loc, int n_seq, int first, int32_t* best,
+                            double* best_loss, float* dis, int32_t* locs, hipStream_t st) {
+    hipLaunchKernelGGL(shapelet_select, dim3(1), dim3(kShpThreads), 0, st, num, loss, n_cand, blocks, n_blocks, min2, loc,
+                       n_seq, first, best, best_loss, dis, locs);
+}
+
+}  // namespace opose

@@ -105,6 +105,11 @@ SIGNATURES = {
     "opose_draw_records": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _P, _P, _I]),
     "opose_draw_motion": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _I, _P, _P, _I]),
     "opose_debug_draw_prims": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "opose_motion_features": (_I, [_P, _P, _P, _I, _I, _I, _P, _I]),
+    "opose_sliding_distance": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _I]),
+    "opose_shapelet_mindist": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _I]),
+    "opose_shapelet_find": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I]),
+    "opose_debug_shapelet_score": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
 }
 EXPORTED = list(SIGNATURES)
 

@@ -1,0 +1,195 @@
+"""Shapelet search over motion data on the device: the reference's srcmx/PreprocessingData.py
+MotionJointFeatures, srcmx/utilmx.py SlidingDistance and srcmx/shapeletmodel.py
+ShapeletMatrixModel.train through libopose's shapelet entry points (include/opose.h states the
+distance, score and selection rules; tests/shapelet_cases.py restates them in NumPy).
+
+Host arrays in give host arrays out.  torch CUDA tensors in give CUDA tensors out, ordered on
+torch's current stream (Handle.torch_call), with no host round trip of the data; the row offsets and
+labels are small host arrays either way."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _native
+from ._native import lib
+
+_HANDLES = {}
+
+
+def default_handle(device: int = 0) -> _native.Handle:
+    """The handle the module-level functions share (one per device, made on first use)."""
+    if device not in _HANDLES:
+        _HANDLES[device] = _native.Handle(device)
+    return _HANDLES[device]
+
+
+def _is_dev(a) -> bool:
+    return hasattr(a, "data_ptr") and a.is_cuda
+
+
+def _offsets(lengths) -> np.ndarray:
+    off = np.zeros(len(lengths) + 1, np.int64)
+    np.cumsum(np.asarray(lengths, np.int64), out=off[1:])
+    return off
+
+
+def _run(handle, dev, fn, *args):
+    if dev:
+        handle.torch_call(fn, *args)
+    else:
+        handle.check(fn(handle.h, *args))
+
+
+def MotionJointFeatures(motiondata, datamode=None, featuremode=0, lengths=None, handle=None):
+    """motiondata [T, C, 3] float64 with C = 18 ('pose') or 60 ('posehand') -> float32 [T, F, 2].
+    lengths: the clips concatenated in motiondata (default: one clip); fills never cross a clip."""
+    import torch
+    dev = _is_dev(motiondata)
+    m = motiondata.contiguous() if dev else np.ascontiguousarray(motiondata, np.float64)
+    if m.ndim != 3 or m.shape[2] != 3 or (dev and m.dtype != torch.float64):
+        raise ValueError("expected float64 motion data [T, C, 3]")
+    T, Cn, _ = m.shape
+    if datamode is None:
+        datamode = {18: "pose", 60: "posehand"}.get(Cn)
+    if datamode not in ("pose", "posehand") or Cn != {"pose": 18, "posehand": 60}[datamode]:
+        raise Exception("please input correct datamode")
+    off = _offsets([T] if lengths is None else lengths)
+    if off[-1] != T:
+        raise ValueError("lengths do not add up to the rows of motiondata")
+    F = 6 if Cn == 18 else 46
+    h = handle or default_handle(m.device.index if dev else 0)
+    out = torch.empty((T, F, 2), dtype=torch.float32, device=m.device) if dev else np.empty((T, F, 2), np.float32)
+    _run(h, dev, lib.opose_motion_features, _native._ptr(m), off.ctypes.data, len(off) - 1, Cn, int(featuremode),
+         _native._ptr(out), _native.DEVICE_IO if dev else 0)
+    return out
+
+
+def _ragged(X):
+    """X: a list of [T_i, D] arrays / tensors, or an [N, D, T] tensor -> (seq [L, D] float32, off, dev)."""
+    import torch
+    if isinstance(X, (list, tuple)):
+        dev = _is_dev(X[0])
+        if dev:
+            seq = torch.cat([x.to(torch.float32) for x in X], dim=0).contiguous()
+        else:
+            seq = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32) for x in X], axis=0))
+        return seq, _offsets([len(x) for x in X]), dev
+    N, D, T = X.shape
+    dev = _is_dev(X)
+    if dev:
+        seq = X.permute(0, 2, 1).reshape(-1, D).to(torch.float32).contiguous()
+    else:
+        seq = np.ascontiguousarray(np.asarray(X, np.float32).transpose(0, 2, 1).reshape(-1, D))
+    return seq, _offsets([T] * N), dev
+
+
+def SlidingDistance(pattern, sequence, handle=None):
+    """The distance of pattern [m, D] to every window of sequence [n, D]: float32 [n - m + 1]."""
+    import torch
+    dev = _is_dev(sequence)
+    if dev:
+        s = sequence.to(torch.float32).contiguous()
+        p = torch.as_tensor(pattern, dtype=torch.float32, device=s.device).contiguous()
+    else:
+        s = np.ascontiguousarray(sequence, np.float32)
+        p = np.ascontiguousarray(pattern, np.float32)
+    if s.ndim == 1:
+        s, p = s.reshape(-1, 1), p.reshape(-1, 1)
+    n, D = s.shape
+    m = len(p)
+    off = _offsets([n])
+    h = handle or default_handle(s.device.index if dev else 0)
+    n_out = max(n - m + 1, 0)
+    out = torch.empty(n_out, dtype=torch.float32, device=s.device) if dev else np.empty(n_out, np.float32)
+    _run(h, dev, lib.opose_sliding_distance, _native._ptr(p), m, _native._ptr(s), off.ctypes.data, 1, D,
+         _native._ptr(out), _native.DEVICE_IO if dev else 0)
+    return out
+
+
+def shapelet_mindist(seq, off, m, cand_seqs, handle=None):
+    """The first stage alone on a ragged batch: (min2, loc) [n_cand, n_seq] (opose_shapelet_mindist)."""
+    import torch
+    dev = _is_dev(seq)
+    off = np.ascontiguousarray(off, np.int64)
+    cs = np.ascontiguousarray(cand_seqs, np.int32)
+    n_seq = len(off) - 1
+    n_cand = int(sum(max(int(off[i + 1] - off[i]) - m + 1, 0) for i in cs if 0 <= i < n_seq))
+    h = handle or default_handle(seq.device.index if dev else 0)
+    if dev:
+        min2 = torch.empty((n_cand, n_seq), dtype=torch.float32, device=seq.device)
+        loc = torch.empty((n_cand, n_seq), dtype=torch.int32, device=seq.device)
+    else:
+        min2, loc = np.empty((n_cand, n_seq), np.float32), np.empty((n_cand, n_seq), np.int32)
+    _run(h, dev, lib.opose_shapelet_mindist, _native._ptr(seq), off.ctypes.data, n_seq, seq.shape[1], int(m),
+         cs.ctypes.data, len(cs), _native._ptr(min2), _native._ptr(loc), _native.DEVICE_IO if dev else 0)
+    return min2, loc
+
+
+def shapelet_find(seq, off, labels, m, max_cands=0, every=False, handle=None):
+    """opose_shapelet_find on a ragged batch: a dict of best [4], loss, dis [n_seq], locs [n_seq] (and,
+    with every=True, every candidate's num and loss).  Device inputs give device outputs."""
+    import torch
+    dev = _is_dev(seq)
+    off = np.ascontiguousarray(off, np.int64)
+    lab = np.ascontiguousarray(np.asarray(labels.cpu() if hasattr(labels, "cpu") else labels) != 0, np.uint8)
+    n_seq, n = len(off) - 1, len(lab)
+    n_cand = int(sum(max(int(off[i + 1] - off[i]) - m + 1, 0) for i in range(min(n, n_seq)) if lab[i]))
+    h = handle or default_handle(seq.device.index if dev else 0)
+    if dev:
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=seq.device)  # noqa: E731
+        best, loss = mk(4, torch.int32), mk(1, torch.float64)
+        dis, locs = mk(n_seq, torch.float32), mk(n_seq, torch.int32)
+        nums, losses = (mk(n_cand, torch.int32), mk(n_cand, torch.float64)) if every else (None, None)
+    else:
+        best, loss = np.empty(4, np.int32), np.empty(1, np.float64)
+        dis, locs = np.empty(n_seq, np.float32), np.empty(n_seq, np.int32)
+        nums, losses = (np.empty(n_cand, np.int32), np.empty(n_cand, np.float64)) if every else (None, None)
+    _run(h, dev, lib.opose_shapelet_find, _native._ptr(seq), off.ctypes.data, n_seq, seq.shape[1], int(m),
+         lab.ctypes.data, n, int(max_cands), _native._ptr(best), _native._ptr(loss), _native._ptr(dis),
+         _native._ptr(locs), _native._ptr(nums) if every else None, _native._ptr(losses) if every else None,
+         _native.DEVICE_IO if dev else 0)
+    return {"best": best, "loss": loss, "dis": dis, "locs": locs, "nums": nums, "losses": losses}
+
+
+class ShapeletMatrixModel:
+    """The reference's brute-force shapelet model: train() keeps the window of a positive clip whose
+    distances to all clips separate the labels best."""
+
+    def __init__(self, handle=None):
+        self.handle = handle
+
+    def train(self, X, labels, m_len, mirror=None, max_cands=0):
+        """X: a list of [T_i, D] arrays or an [N, D, T] tensor; labels: N values 0 / 1.  Sets
+        shapeindex, cand (the window's start in clip shapeindex), locs (int16), dis, score.
+        mirror 'x-mirror' / 'y-mirror': the copies with the even / odd feature columns negated are
+        appended (made with torch on the device); locs, dis and the boolean `mirrored` are then the
+        chosen of each pair.  (The reference's ShapeletMatrixModel_LR fails in these modes.)"""
+        import torch
+        seq, off, dev = _ragged(X)
+        n = len(off) - 1
+        if mirror is not None:
+            if mirror not in ("x-mirror", "y-mirror"):
+                raise ValueError("mirror must be None, 'x-mirror' or 'y-mirror'")
+            if not dev:
+                device = torch.device("cuda", self.handle.device if self.handle else 0)
+                seq = torch.from_numpy(seq).to(device)
+            sign = torch.ones(seq.shape[1], dtype=torch.float32, device=seq.device)
+            sign[(0 if mirror == "x-mirror" else 1)::2] = -1
+            seq = torch.cat((seq, seq * sign), dim=0)
+            off = np.concatenate((off, off[1:] + off[-1]))
+        res = shapelet_find(seq, off, labels, m_len, max_cands, handle=self.handle)
+        host = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in res.items() if v is not None}
+        best, dis, locs = host["best"], host["dis"], host["locs"]
+        self.shapeindex, self.cand = int(best[0]), int(best[1])
+        self.score = int(best[2]) / n
+        self.loss = float(host["loss"][0])
+        if mirror is None:
+            self.mirrored = np.zeros(n, bool)
+        else:  # the smaller distance of each pair, the original on a tie.  sqrt keeps the order of s;
+            # two s one rounding apart may share a square root, and the pair then reports the original
+            # (same dis; the score was taken from the s values themselves)
+            self.mirrored = dis[n:] < dis[:n]
+        pick = np.arange(n) + n * self.mirrored
+        self.dis = dis[pick].astype(np.float64)
+        self.locs = locs[pick].astype(np.int16)
+        return self
