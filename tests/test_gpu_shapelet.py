@@ -23,6 +23,8 @@ K = _constants()
 TR, TC, DC, MAXM, MAXD, MAXSEQ, FEAT_ROWS = (K[k] for k in ("kShpTR", "kShpTC", "kShpDC", "kShpMaxM", "kShpMaxD",
                                                               "kShpMaxSeq", "kFeatRows"))
 SUB = K["kShpThreads"] // TR  # threads that share one candidate start's positions
+T, DEFAULT_CANDS = K["kShpThreads"], K["kShpDefaultCands"]
+assert K == sc.K  # the edge cases of shapelet_cases.py are cut to the same constants
 
 
 @pytest.fixture(scope="module")
@@ -47,21 +49,21 @@ def random_seqs(seed, lengths, D, integer=False):
     return [rng.standard_normal((n, D)).astype(np.float32) for n in lengths]
 
 
-def check_mindist(sh, seqs, m, cands=None):
+def check_mindist(sh, seqs, m, cands=None, want=None):
     cands = list(range(len(seqs))) if cands is None else cands
     seq, off = ragged(seqs)
     min2, loc = sh.shapelet_mindist(seq, off, m, cands)
-    want2, wantloc = sc.mindist(seqs, cands, m)
+    want2, wantloc = want or sc.mindist(seqs, cands, m)
     assert min2.shape == want2.shape
     assert np.array_equal(bits(min2), bits(want2))
     assert np.array_equal(loc, wantloc)
     return min2, loc
 
 
-def check_find(sh, seqs, labels, m, max_cands=0):
+def check_find(sh, seqs, labels, m, max_cands=0, want=None):
     seq, off = ragged(seqs)
     got = sh.shapelet_find(seq, off, labels, m, max_cands, every=True)
-    want = sc.find(seqs, labels, m)
+    want = want or sc.find(seqs, labels, m)
     assert got["best"].tolist() == [want["shapeindex"], want["cand"], want["num"], want["n_cand"]]
     assert got["loss"][0] == want["loss"]
     assert np.array_equal(got["nums"], want["nums"])
@@ -309,3 +311,130 @@ def test_shape_and_argument_errors(sh):
     with pytest.raises(_native.OposeError) as e:
         sh.MotionJointFeatures(np.zeros((4, 18, 3)), lengths=[4], featuremode=3)
     assert e.value.code == _native.OPOSE_E_ARG
+
+
+# ---------------------------------------------------------------- 5. past one workgroup, at the limits
+# The cases of shapelet_cases.py (tests/test_shapelet_cases.py shows that each has the geometry and
+# the ties it claims); T = kShpThreads.
+@pytest.mark.parametrize("name", sc.SLIDING_CASES)
+def test_sliding_distance_over_several_workgroups(sh, name):
+    """sliding_distance's row blockIdx.x * T + threadIdx.x: batches of T - 1, T, T + 1 and 2 T + 5 rows,
+    a sequence that ends at row T, one that straddles it (its tail rows, which have no window, in
+    the second workgroup), and seq_of_row's search over 300 sequences.  The output is prefilled, so
+    a value not written, or written past the end, shows."""
+    from src import _native
+    pat, seqs = sc.sliding_case(name)
+    seq, off = ragged(seqs)
+    m, n_seq = len(pat), len(seqs)
+    want = sc.sliding_distance(pat, seqs)
+    assert len(want) == len(seq) - n_seq * (m - 1)
+    handle = sh.default_handle()
+    patd, seqd = torch.from_numpy(pat).cuda(), torch.from_numpy(seq).cuda()
+    dist = torch.full((len(want) + T,), -1.0, dtype=torch.float32, device="cuda")
+    handle.torch_call(_native.lib.opose_sliding_distance, patd.data_ptr(), m, seqd.data_ptr(), off.ctypes.data, n_seq,
+                      seq.shape[1], dist.data_ptr(), _native.DEVICE_IO)
+    got = dist.cpu().numpy()
+    assert np.array_equal(bits(got[:len(want)]), bits(want))
+    assert (got[len(want):] == -1.0).all()
+    host = np.full(len(want), -1.0, np.float32)
+    handle.check(_native.lib.opose_sliding_distance(handle.h, pat.ctypes.data, m, seq.ctypes.data, off.ctypes.data,
+                                                    n_seq, seq.shape[1], host.ctypes.data, 0))
+    assert np.array_equal(bits(host), bits(want))
+
+
+@pytest.mark.parametrize("name", sc.SCORE_CASES)
+def test_score_and_select_past_their_first_trip(sh, name):
+    """shapelet_score's key fill, rank count and label scatter (loops that step by T over n_labels:
+    n_labels of T - 1, T, T + 1, 2 T + 3 and kShpMaxSeq, equal keys at k and k + T -- one thread, two
+    trips -- and at k and k + T + 1, every key equal, all / one positive, the pair minimum at
+    k + n_labels for k >= T), and shapelet_select's candidate walk and reduction (n_cand of T - 1, T,
+    T + 1, 2 T + 7; the last candidate the winner; identical rows tying fully across trips and across
+    threads, the later member in the lower thread; equal num with the smaller loss later)."""
+    from src._native import lib
+    rows, labels = sc.score_case(name)
+    want_nums, want_losses, w = sc.score_expected(name)
+    rows = np.ascontiguousarray(rows, np.float32)
+    n_cand, n_seq = rows.shape
+    handle = sh.default_handle()
+    nums, losses = np.full(n_cand, -7, np.int32), np.full(n_cand, -1.0, np.float64)
+    winner, wloss = np.full(4, -7, np.int32), np.full(1, -1.0, np.float64)
+    handle.check(lib.opose_debug_shapelet_score(handle.h, rows.ctypes.data, n_cand, n_seq, labels.ctypes.data,
+                                                len(labels), nums.ctypes.data, losses.ctypes.data,
+                                                winner.ctypes.data, wloss.ctypes.data))
+    assert np.array_equal(nums, want_nums)
+    assert np.array_equal(losses.view(np.uint64), want_losses.view(np.uint64))
+    assert winner.tolist() == [0, w, int(want_nums[w]), n_cand]
+    assert wloss.view(np.uint64)[0] == want_losses.view(np.uint64)[w]
+
+
+@pytest.mark.parametrize("name", sc.MINDIST_CASES)
+def test_mindist_long_windows_chunks_and_limits(sh, name):
+    """shapelet_mindist where m > kShpTC meets several candidate and position blocks (the band E, the
+    row counts na / nb, the c0 + b >= ylen tail), D a whole number of kShpDC chunks and one short of
+    it, D = kShpMaxD, the workload's shape (m 25, D 92), 300 and kShpMaxSeq sequences (grid y), and
+    a window of m = kShpTC + 5 planted in three position blocks: the lowest location wins."""
+    seqs, m, cands = sc.mindist_case(name)
+    check_mindist(sh, seqs, m, cands, want=sc.mindist_expected(name))
+
+
+def test_find_on_the_workload_shape(sh):
+    """The shape scripts/shapelet_timing.py times (m 25, D 92), made small, through the whole search."""
+    seqs, m, _ = sc.mindist_case("workload")
+    got, want = check_find(sh, seqs, np.array([1, 0, 1, 0, 1, 0], np.uint8), m)
+    assert want["n_cand"] == sum(len(seqs[i]) - m + 1 for i in (0, 2, 4))
+
+
+def test_find_cuts_a_chunk_at_its_default_size(sh):
+    """max_cands = 0 with more than kShpDefaultCands candidates: the default path cuts a chunk, the
+    per-candidate nums / losses of the second chunk land behind the first's (in the caller's device
+    memory too), and the winner's full tie with a candidate of the second chunk stays with the winner."""
+    seqs, labels, m = sc.find_case("default_chunks")
+    want = sc.find_expected("default_chunks")
+    host, _ = check_find(sh, seqs, labels, m, want=want)
+    assert host["best"][3] == want["n_cand"] and want["n_cand"] > DEFAULT_CANDS
+    seq, off = ragged(seqs)
+    dev = sh.shapelet_find(torch.from_numpy(seq).cuda(), off, labels, m, every=True)
+    for k, v in host.items():
+        assert dev[k].is_cuda and np.array_equal(dev[k].cpu().numpy(), v), k
+
+
+def test_find_full_tie_across_chunks_stays_with_the_earlier_candidate(sh):
+    """shapelet_select's take: the running winner is replaced only by a strictly better candidate.
+    The two planted windows tie fully; in one chunk the reduction decides, in two the strict <."""
+    seqs, labels, m = sc.find_case("tie")
+    want = sc.find_expected("tie")
+    one, _ = check_find(sh, seqs, labels, m, want=want)
+    two, _ = check_find(sh, seqs, labels, m, max_cands=sc.TIE_FIND_SPLIT, want=want)
+    assert one["best"][:2].tolist() == [1, sc.TIE_FIND_ROWS[0]]
+    for k in one:
+        assert np.array_equal(one[k], two[k]), k
+
+
+@pytest.mark.parametrize("name", list(sc.CUT_WINNERS))
+def test_find_chunk_cut_inside_a_candidate_block(sh, name):
+    """max_cands not a multiple of kShpTR cuts a sequence's block of starts: the winner in the cut
+    block's two parts and in the entry after them (shapelet_select's table walk from out0)."""
+    seqs, labels, m = sc.find_case(name)
+    want = sc.find_expected(name)
+    cut, _ = check_find(sh, seqs, labels, m, max_cands=sc.CUT_CANDS, want=want)
+    assert cut["best"][:2].tolist() == list(sc.CUT_WINNERS[name])
+    one, _ = check_find(sh, seqs, labels, m, want=want)
+    for k in one:
+        assert np.array_equal(one[k], cut[k]), k
+
+
+@pytest.mark.parametrize("joints", [18, 60])
+@pytest.mark.parametrize("name", sc.FEATURE_CASES)
+def test_feature_edges_equal_the_statement(sh, name, joints):
+    """feat_compute / seq_of_row with empty sequences (first, two in the middle, last), L of kFeatRows
+    and kFeatRows + 1, 300 one-row sequences (the search), and the fills at the fill block's edges:
+    a carry from the previous sequence in the previous block refused beside one accepted, a sequence
+    that starts / ends on a block boundary with zeros there (modes 0 / 1 and the nearby fill of mode 2)."""
+    mot, lengths = sc.feature_case(name, joints)
+    for mode in (0, 1, 2):
+        got = sh.MotionJointFeatures(mot, featuremode=mode, lengths=lengths)
+        want = sc.motion_features(mot, lengths, mode)
+        assert got.dtype == np.float32 and got.shape == want.shape
+        assert np.array_equal(bits(got), bits(want)), mode
+    dev = sh.MotionJointFeatures(torch.from_numpy(mot).cuda(), featuremode=2, lengths=lengths)
+    assert dev.is_cuda and np.array_equal(bits(dev.cpu().numpy()), bits(sc.motion_features(mot, lengths, 2)))
