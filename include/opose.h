@@ -32,6 +32,8 @@
  *   SlidingDistance(_torch)        srcmx/utilmx.py:330-372   opose_sliding_distance
  *   ShapeletMatrixModel.train      srcmx/shapeletmodel.py:   opose_shapelet_find;
  *                                  97-209                    opose_shapelet_mindist (first stage)
+ *   ShapeletsFinding.train's       srcmx/shapeletlearning    opose_shapelet_find_lengths;
+ *   m_len loop                     .py:123-175               opose_shapelet_mindist_lengths
  *
  * Conventions: plain pointers and sizes only; 0 = OK, negative = error (see opose_status).
  * Host pointers are caller-owned and read-only; the library copies them. A handle owns one
@@ -439,6 +441,44 @@ int opose_shapelet_mindist(opose_t* h, const float* seq, const int64_t* off, int
 int opose_shapelet_find(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int m,
                         const uint8_t* labels, int n_labels, int max_cands, int32_t* best, double* best_loss,
                         float* dis, int32_t* locs, int32_t* cand_num, double* cand_loss, int flags);
+
+/* Several window lengths in one pass (the m_len loop of ShapeletsFinding.train,
+ * srcmx/shapeletlearning.py:123-175, which searches range(15, 40, 2) over the same clips).  e(a, b)
+ * does not depend on the window length, and the sum s(r, c) runs k ascending from +0, so its partial
+ * sum after m terms is the s of length m: the distances are formed once, for the longest length, and
+ * every shorter length is a snapshot of the same walk.  Per length the results equal the
+ * single-length call's bit for bit.
+ *
+ * m_lens int32 [n_lens], host memory: 1 <= n_lens <= 16, every length >= 1, strictly ascending, the
+ * last <= 128, and every sequence at least the last length long.  Checked before anything is
+ * launched: OPOSE_E_ARG for n_lens < 1, a length below 1 or lengths that do not ascend strictly;
+ * OPOSE_E_SHAPE for n_lens > 16, a last length beyond the limit or a sequence shorter than the last
+ * length; the ragged batch otherwise as above.  A start r of sequence i is a candidate of length
+ * m_l when r + m_l <= len_i, and a position c of sequence j is compared at length m_l when
+ * c + m_l <= len_j: no window crosses into the next sequence.
+ *
+ * With n_cand_l = the sum of len_i - m_l + 1 over the candidate sequences, length l's results are
+ * the dense block [n_cand_l][n_seq] that opose_shapelet_mindist(m_l) writes, rows by (position in
+ * cand_seqs, r), and the blocks follow one another: length l's first row is row
+ * n_cand_0 + ... + n_cand_{l-1} of min2 / loc (sum of all n_cand_l rows of n_seq values each). */
+int opose_shapelet_mindist_lengths(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D,
+                                   const int32_t* m_lens, int n_lens, const int32_t* cand_seqs, int n_cand_seqs,
+                                   float* min2, int32_t* loc, int flags);
+
+/* opose_shapelet_find for every length of m_lens: best int32 [n_lens][4] (per length: the winner's
+ * sequence, its start, its num, the candidates scored at that length), best_loss float64 [n_lens],
+ * dis float32 [n_lens][n_seq], locs int32 [n_lens][n_seq]; cand_num int32 / cand_loss float64: every
+ * candidate's num and loss per length, concatenated as the rows of opose_shapelet_mindist_lengths
+ * are (sum of n_cand_l values), or both NULL.  Labels and candidates as in opose_shapelet_find.
+ * max_cands (0: the library's default) bounds the candidates of the shortest length per chunk; the
+ * workspace is n_lens times that.  Each length keeps its own winner on the device across the
+ * chunks; a chunk that holds only starts too late in their clips for a length scores nothing at
+ * that length.  Per length the results equal opose_shapelet_find(m_l) bit for bit, whatever the
+ * chunking. */
+int opose_shapelet_find_lengths(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D,
+                                const int32_t* m_lens, int n_lens, const uint8_t* labels, int n_labels,
+                                int max_cands, int32_t* best, double* best_loss, float* dis, int32_t* locs,
+                                int32_t* cand_num, double* cand_loss, int flags);
 
 /* Hand on N crops uint8 [H][W][3] (util.handDetect gives squares): peaks [N][21][3]
  * (x, y, score), found [N][21] (0 = part missing, the reference's [0,0,0] row). */

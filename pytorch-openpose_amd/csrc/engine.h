@@ -429,9 +429,10 @@ struct opose_ctx {
     opose::DevBuf draw_prims, draw_counts, draw_status, draw_motion, draw_out;
     // shapelet search (engine_shapelet.cpp): staged inputs (sequences, offsets, labels, pattern or
     // MotionMat rows), the block table, a chunk's minima / locations / scores, the running winner
-    // and staged outputs
+    // and staged outputs; for the several-lengths calls also the per-(entry, length) rows and the
+    // per-length tables handed to the selection
     opose::DevBuf shp_seq, shp_off, shp_labels, shp_in, shp_blocks, shp_min2, shp_loc, shp_num, shp_loss, shp_best,
-        shp_carry, shp_out;
+        shp_carry, shp_out, shp_lrows, shp_sel;
     // opose_batch_hand_extract cuts its 2N crops into chunks the conv kernels can address (as
     // opose_hand_infer_crops does); OPOSE_EXTRACT_CHUNK=n at handle creation: n crops per chunk
     // instead (tests/test_gpu_hand_extract.py runs a small batch in two chunks)

@@ -86,6 +86,46 @@ static void run_mindist(opose_ctx* h, const float* seq, const int64_t* off, int 
     h->prof_end(pe);
 }
 
+// The window lengths of a several-lengths call: 1 .. kShpMaxLens of them, each at least 1, strictly
+// ascending.  (shp_check on the last length holds the rest: its limit, and every sequence that long.)
+static int shp_lens_check(opose_ctx* h, const int32_t* m_lens, int n_lens, ShpLens* lens) {
+    if (n_lens < 1) {
+        h->err = "shapelet: at least one window length";
+        return OPOSE_E_ARG;
+    }
+    if (n_lens > kShpMaxLens) {
+        h->err = "shapelet: more window lengths than one call supports";
+        return OPOSE_E_SHAPE;
+    }
+    *lens = ShpLens{};
+    lens->n = n_lens;
+    for (int l = 0; l < n_lens; ++l) {
+        if (m_lens[l] < 1 || (l && m_lens[l] <= m_lens[l - 1])) {
+            h->err = "shapelet: window lengths must be positive and strictly ascending";
+            return OPOSE_E_ARG;
+        }
+        lens->m[l] = m_lens[l];
+    }
+    return OPOSE_OK;
+}
+
+// the starts of table entry b that are valid at window length m: its first so many
+static int shp_valid_at(const int64_t* off, const ShpBlock& b, int m) {
+    const int64_t P = off[b.seq + 1] - off[b.seq] - m + 1;
+    return (int)std::min<int64_t>(std::max<int64_t>(P - b.r0, 0), b.nvalid);
+}
+
+static void run_mindist_lengths(opose_ctx* h, const float* seq, const int64_t* off, int n_seq, int D,
+                                const ShpLens& lens, const ShpBlock* blocks, const ShpLenRows* rows, int nb, int nc,
+                                int64_t L, float* min2, int32_t* loc) {
+    ProfEntry pe;
+    const int mx = lens.m[lens.n - 1];
+    h->prof_begin(pe, "shapelet_mindist_lengths", 3.0 * nc * (double)(L - (int64_t)n_seq * (mx - 1)) * D,
+                  8.0 * nc * n_seq * lens.n);
+    launch_shapelet_mindist_lengths(seq, off, n_seq, D, lens, blocks, rows, nb, min2, loc, h->stream);
+    h->prof_end(pe);
+}
+
 static void run_score(opose_ctx* h, const float* min2, int nc, int n_seq, int n_labels, const uint8_t* labels, int negs,
                       int32_t* num, double* loss) {
     ProfEntry pe;
@@ -315,6 +355,162 @@ int opose_shapelet_find(opose_t* h, const float* seq, const int64_t* off, int n_
             if (all) {
                 OPOSE_HIP_CHECK(hipMemcpyAsync(cand_num, nd, (size_t)total * 4, hipMemcpyDeviceToHost, h->stream));
                 OPOSE_HIP_CHECK(hipMemcpyAsync(cand_loss, sl, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream));
+            }
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_shapelet_mindist_lengths(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D,
+                                   const int32_t* m_lens, int n_lens, const int32_t* cand_seqs, int n_cand_seqs,
+                                   float* min2, int32_t* loc, int flags) {
+    if (!h || !seq || !off || !m_lens || !cand_seqs || !min2 || !loc || n_cand_seqs < 1) return OPOSE_E_ARG;
+    ShpLens lens;
+    if (const int rc = shp_lens_check(h, m_lens, n_lens, &lens)) return rc;
+    if (const int rc = shp_check(h, off, n_seq, D, lens.m[n_lens - 1])) return rc;
+    for (int i = 0; i < n_cand_seqs; ++i)
+        if (cand_seqs[i] < 0 || cand_seqs[i] >= n_seq) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const bool od = flags & OPOSE_OUT_DEVICE;
+        const int64_t L = off[n_seq];
+        std::vector<ShpBlock> blocks;
+        std::vector<ShpChunk> chunks;
+        const std::vector<int> cands(cand_seqs, cand_seqs + n_cand_seqs);
+        const int64_t nc0 = shp_table(off, lens.m[0], cands, INT32_MAX, blocks, chunks);
+        // length l's block of rows follows the blocks of the shorter lengths, compacted
+        std::vector<ShpLenRows> rows(blocks.size() * n_lens);
+        int64_t total = 0;
+        for (int l = 0; l < n_lens; ++l)
+            for (size_t b = 0; b < blocks.size(); ++b) {
+                const int nv = shp_valid_at(off, blocks[b], lens.m[l]);
+                rows[b * n_lens + l] = ShpLenRows{(int32_t)total, nv};
+                total += nv;
+            }
+        if (nc0 > INT32_MAX || total > INT32_MAX)
+            throw std::invalid_argument("shapelet: too many candidates for one call");
+        const size_t n_out = (size_t)total * n_seq;
+        const float* sd = shp_stage(h, h->shp_seq, seq, (size_t)L * D, flags & OPOSE_IN_DEVICE);
+        const int64_t* offd = shp_stage(h, h->shp_off, off, (size_t)n_seq + 1, false);
+        float* md = od ? min2 : h->shp_min2.ensure<float>(n_out, h->stream);
+        int32_t* ld = od ? loc : h->shp_loc.ensure<int32_t>(n_out, h->stream);
+        const ShpBlock* bd = shp_upload(h, h->shp_blocks, blocks);
+        const ShpLenRows* rd = shp_upload(h, h->shp_lrows, rows);
+        run_mindist_lengths(h, sd, offd, n_seq, D, lens, bd, rd, (int)blocks.size(), (int)nc0, L, md, ld);
+        if (!od) {
+            OPOSE_HIP_CHECK(hipMemcpyAsync(min2, md, n_out * 4, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(loc, ld, n_out * 4, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_shapelet_find_lengths(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D,
+                                const int32_t* m_lens, int n_lens, const uint8_t* labels, int n_labels, int max_cands,
+                                int32_t* best, double* best_loss, float* dis, int32_t* locs, int32_t* cand_num,
+                                double* cand_loss, int flags) {
+    if (!h || !seq || !off || !m_lens || !labels || !best || !best_loss || !dis || !locs) return OPOSE_E_ARG;
+    if (max_cands < 0 || (cand_num == nullptr) != (cand_loss == nullptr)) return OPOSE_E_ARG;
+    int negs = 0;
+    if (const int rc = shp_labels_check(h, labels, n_labels, n_seq, &negs)) return rc;
+    if (negs == n_labels) {
+        h->err = "shapelet: no positive sequence, so no candidate";
+        return OPOSE_E_ARG;
+    }
+    ShpLens lens;
+    if (const int rc = shp_lens_check(h, m_lens, n_lens, &lens)) return rc;
+    if (const int rc = shp_check(h, off, n_seq, D, lens.m[n_lens - 1])) return rc;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const bool od = flags & OPOSE_OUT_DEVICE;
+        const int64_t L = off[n_seq];
+        const size_t ns = (size_t)n_seq, nl = (size_t)n_lens;
+        std::vector<int> cands;
+        for (int i = 0; i < n_labels; ++i)
+            if (labels[i]) cands.push_back(i);
+        // the chunks are those of the shortest length, which has the most candidates
+        std::vector<ShpBlock> blocks;
+        std::vector<ShpChunk> chunks;
+        const int64_t total0 = shp_table(off, lens.m[0], cands, max_cands ? max_cands : kShpDefaultCands, blocks, chunks);
+        int cap = 0;
+        for (const ShpChunk& c : chunks) cap = std::max(cap, c.nc);
+        if (total0 > INT32_MAX || (int64_t)cap * n_lens > INT32_MAX)
+            throw std::invalid_argument("shapelet: too many candidates for one call");
+        // Per chunk and length: the rows the distance kernel writes (length l's block of the
+        // workspace starts at row l * cap), and the table the selection reads, which leaves out the
+        // entries without a valid start at that length and counts its rows from the block's first.
+        struct Part {
+            size_t t0;  // first entry in sel
+            int nt, nc;
+        };
+        std::vector<ShpLenRows> rows(blocks.size() * nl);
+        std::vector<ShpBlock> sel;
+        std::vector<Part> parts(chunks.size() * nl);
+        std::vector<size_t> first_out(nl + 1, 0);  // length l's first candidate among all lengths' candidates
+        for (size_t ci = 0; ci < chunks.size(); ++ci)
+            for (int l = 0; l < n_lens; ++l) {
+                Part p{sel.size(), 0, 0};
+                for (int b = chunks[ci].b0; b < chunks[ci].b0 + chunks[ci].nb; ++b) {
+                    const int nv = shp_valid_at(off, blocks[b], lens.m[l]);
+                    rows[(size_t)b * nl + l] = ShpLenRows{l * cap + p.nc, nv};
+                    if (nv) {
+                        sel.push_back(ShpBlock{blocks[b].seq, blocks[b].r0, nv, p.nc});
+                        p.nt++;
+                        p.nc += nv;
+                    }
+                }
+                parts[ci * nl + l] = p;
+                first_out[l + 1] += (size_t)p.nc;
+            }
+        for (int l = 0; l < n_lens; ++l) first_out[l + 1] += first_out[l];
+        const float* sd = shp_stage(h, h->shp_seq, seq, (size_t)L * D, flags & OPOSE_IN_DEVICE);
+        const int64_t* offd = shp_stage(h, h->shp_off, off, (size_t)n_seq + 1, false);
+        const uint8_t* yd = shp_stage(h, h->shp_labels, labels, (size_t)n_labels, false);
+        float* md = h->shp_min2.ensure<float>(nl * cap * ns, h->stream);
+        int32_t* ld = h->shp_loc.ensure<int32_t>(nl * cap * ns, h->stream);
+        // every candidate's num / loss when asked for (per length, concatenated), else one chunk's
+        const bool all = cand_num != nullptr;
+        const size_t n_score = all ? first_out[nl] : nl * cap;
+        int32_t* nd = all && od ? cand_num : h->shp_num.ensure<int32_t>(n_score, h->stream);
+        double* sl = all && od ? cand_loss : h->shp_loss.ensure<double>(n_score, h->stream);
+        // the winners when the outputs are host memory:
+        // int32 best[n_lens][4] | double best_loss[n_lens] | float dis[n_lens][n_seq] | int32 locs[n_lens][n_seq]
+        uint8_t* wb = od ? nullptr : h->shp_best.ensure<uint8_t>(nl * shp_best_bytes(n_seq), h->stream);
+        int32_t* bestd = od ? best : reinterpret_cast<int32_t*>(wb);
+        double* blossd = od ? best_loss : reinterpret_cast<double*>(wb + 16 * nl);
+        float* disd = od ? dis : reinterpret_cast<float*>(wb + 24 * nl);
+        int32_t* locsd = od ? locs : reinterpret_cast<int32_t*>(wb + 24 * nl + 4 * nl * ns);
+        const ShpBlock* bd = shp_upload(h, h->shp_blocks, blocks);
+        const ShpLenRows* rd = shp_upload(h, h->shp_lrows, rows);
+        const ShpBlock* seld = shp_upload(h, h->shp_sel, sel);
+        std::vector<size_t> done(nl, 0);
+        for (size_t ci = 0; ci < chunks.size(); ++ci) {
+            const ShpChunk& c = chunks[ci];
+            run_mindist_lengths(h, sd, offd, n_seq, D, lens, bd + c.b0, rd + (size_t)c.b0 * nl, c.nb, c.nc, L, md, ld);
+            for (size_t l = 0; l < nl; ++l) {
+                const Part& p = parts[ci * nl + l];
+                if (!p.nc) continue;  // only tail starts in this chunk: the length keeps its winner
+                const float* ml = md + l * cap * ns;
+                int32_t* cn = nd + (all ? first_out[l] + done[l] : l * cap);
+                double* cl = sl + (all ? first_out[l] + done[l] : l * cap);
+                run_score(h, ml, p.nc, n_seq, n_labels, yd, negs, cn, cl);
+                run_select(h, cn, cl, p.nc, seld + p.t0, p.nt, ml, ld + l * cap * ns, n_seq, done[l] == 0, bestd + 4 * l,
+                           blossd + l, disd + l * ns, locsd + l * ns);
+                done[l] += (size_t)p.nc;
+            }
+        }
+        if (!od) {
+            OPOSE_HIP_CHECK(hipMemcpyAsync(best, bestd, 16 * nl, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(best_loss, blossd, 8 * nl, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(dis, disd, 4 * nl * ns, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(locs, locsd, 4 * nl * ns, hipMemcpyDeviceToHost, h->stream));
+            if (all) {
+                OPOSE_HIP_CHECK(hipMemcpyAsync(cand_num, nd, first_out[nl] * 4, hipMemcpyDeviceToHost, h->stream));
+                OPOSE_HIP_CHECK(hipMemcpyAsync(cand_loss, sl, first_out[nl] * 8, hipMemcpyDeviceToHost, h->stream));
             }
             OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
         }

@@ -1,5 +1,6 @@
 // shapelet.h — limits and tile constants of the shapelet search (shapelet.hip, engine_shapelet.cpp).
-// tests/test_gpu_shapelet.py parses the constants below, so its edge lengths follow the code.
+// tests/shapelet_cases.py and the shapelet GPU tests parse the constants below, so their edge lengths
+// follow the code.
 #pragma once
 #include <cstdint>
 
@@ -17,6 +18,8 @@ constexpr int kShpTC = 32;
 constexpr int kShpDC = 16;
 constexpr int kShpThreads = 256;
 constexpr int kShpSub = kShpThreads / kShpTR;  // threads sharing one candidate start's positions
+// shapelet_mindist_lengths: window lengths one call may share its distances among
+constexpr int kShpMaxLens = 16;
 // opose_shapelet_find: candidates per chunk when the caller passes max_cands = 0
 constexpr int kShpDefaultCands = 2048;
 // motion_features: rows per fill block (the carry of the forward fill crosses these)
@@ -27,6 +30,17 @@ constexpr int kFeatThreads = 256;
 // launch's output that start r0 writes
 struct ShpBlock {
     int32_t seq, r0, nvalid, out0;
+};
+
+// shapelet_mindist_lengths: the ascending window lengths, passed by value as a kernel argument
+struct ShpLens {
+    int32_t n;
+    int32_t m[kShpMaxLens];
+};
+// per (table entry, length): the entry's starts that are valid at that length -- its first nvalid --
+// and the output row the first of them writes
+struct ShpLenRows {
+    int32_t out0, nvalid;
 };
 
 }  // namespace opose

@@ -218,6 +218,44 @@ constexpr int kShpND = kShpTR + kShpTC - 1;    // diagonals of a tile
 static_assert(kShpThreads == kShpTR * kShpSub, "threads = starts x sub-positions");
 static_assert((kShpNA * kShpND + (kShpNA + kShpNB) * (kShpDC + 1)) * 4 <= 65536, "static LDS");
 
+// Step 1 of a position block, shared by shapelet_mindist and shapelet_mindist_lengths: the band E
+// (na rows of kShpND diagonals) of candidate rows xo .. xo + xrows - 1 against target rows
+// yo + c0 .. (nb of them, as far as the target's ylen rows reach), through the staging tiles xs
+// [na][kShpDC + 1] and ys [nb][kShpDC + 1].  An entry is accumulated by one thread, d ascending; an
+// entry of a row beyond xrows or ylen stays +0 and no row outside the two clips is read.  Ends
+// before the barrier that makes E visible.
+__device__ inline void shp_fill_band(float* __restrict__ E, float* __restrict__ xs, float* __restrict__ ys,
+                                     const float* __restrict__ seq, int64_t xo, int xrows, int64_t yo, int ylen,
+                                     int c0, int na, int nb, int D, int t) {
+    const int nent = na * kShpND;
+    for (int e = t; e < nent; e += kShpThreads) E[e] = 0.0f;
+    for (int d0 = 0; d0 < D; d0 += kShpDC) {
+        const int dc = min(kShpDC, D - d0);
+        __syncthreads();  // the previous chunk's readers are done
+        for (int i = t; i < na * kShpDC; i += kShpThreads) {
+            const int a = i / kShpDC, d = i % kShpDC;
+            xs[a * (kShpDC + 1) + d] = (a < xrows && d < dc) ? seq[(xo + a) * D + d0 + d] : 0.0f;
+        }
+        for (int i = t; i < nb * kShpDC; i += kShpThreads) {
+            const int b = i / kShpDC, d = i % kShpDC;
+            ys[b * (kShpDC + 1) + d] = (c0 + b < ylen && d < dc) ? seq[(yo + c0 + b) * D + d0 + d] : 0.0f;
+        }
+        __syncthreads();
+        for (int e = t; e < nent; e += kShpThreads) {  // an entry stays with its thread
+            const int a = e / kShpND, b = a + e % kShpND - (kShpTR - 1);
+            if (a >= xrows || b < 0 || b >= nb || c0 + b >= ylen) continue;  // no output reads it
+            const float* x = xs + a * (kShpDC + 1);
+            const float* y = ys + b * (kShpDC + 1);
+            float acc = E[e];
+            for (int d = 0; d < dc; ++d) {
+                const float v = x[d] - y[d];
+                acc = acc + v * v;
+            }
+            E[e] = acc;
+        }
+    }
+}
+
 __global__ __launch_bounds__(kShpThreads) void shapelet_mindist(const float* __restrict__ seq,
                                                                 const int64_t* __restrict__ off, int n_seq, int D, int m,
                                                                 const ShpBlock* __restrict__ blocks,
@@ -231,37 +269,12 @@ __global__ __launch_bounds__(kShpThreads) void shapelet_mindist(const float* __r
     const int xrows = blk.nvalid + m - 1;
     const int64_t yo = off[j];
     const int ylen = (int)(off[j + 1] - yo), P = ylen - m + 1;
-    const int na = kShpTR + m - 1, nb = kShpTC + m - 1, nent = na * kShpND;
+    const int na = kShpTR + m - 1, nb = kShpTC + m - 1;
     const int r = t / kShpSub, sub = t % kShpSub;
     uint32_t best = 0xffffffffu;
     int bloc = 0;
     for (int c0 = 0; c0 < P; c0 += kShpTC) {
-        for (int e = t; e < nent; e += kShpThreads) E[e] = 0.0f;
-        for (int d0 = 0; d0 < D; d0 += kShpDC) {
-            const int dc = min(kShpDC, D - d0);
-            __syncthreads();  // the previous chunk's readers are done
-            for (int i = t; i < na * kShpDC; i += kShpThreads) {
-                const int a = i / kShpDC, d = i % kShpDC;
-                xs[a * (kShpDC + 1) + d] = (a < xrows && d < dc) ? seq[(xo + a) * D + d0 + d] : 0.0f;
-            }
-            for (int i = t; i < nb * kShpDC; i += kShpThreads) {
-                const int b = i / kShpDC, d = i % kShpDC;
-                ys[b * (kShpDC + 1) + d] = (c0 + b < ylen && d < dc) ? seq[(yo + c0 + b) * D + d0 + d] : 0.0f;
-            }
-            __syncthreads();
-            for (int e = t; e < nent; e += kShpThreads) {  // an entry stays with its thread
-                const int a = e / kShpND, b = a + e % kShpND - (kShpTR - 1);
-                if (a >= xrows || b < 0 || b >= nb || c0 + b >= ylen) continue;  // no output reads it
-                const float* x = xs + a * (kShpDC + 1);
-                const float* y = ys + b * (kShpDC + 1);
-                float acc = E[e];
-                for (int d = 0; d < dc; ++d) {
-                    const float v = x[d] - y[d];
-                    acc = acc + v * v;
-                }
-                E[e] = acc;
-            }
-        }
+        shp_fill_band(E, xs, ys, seq, xo, xrows, yo, ylen, c0, na, nb, D, t);
         __syncthreads();
         if (r < blk.nvalid) {
             for (int c = sub; c < kShpTC && c0 + c < P; c += kShpSub) {
@@ -301,6 +314,109 @@ void launch_shapelet_mindist(const float* seq, const int64_t* off, int n_seq, in
                              int n_blocks, float* min2, int32_t* loc, hipStream_t st) {
     hipLaunchKernelGGL(shapelet_mindist, dim3(n_blocks, n_seq), dim3(kShpThreads), 0, st, seq, off, n_seq, D, m, blocks,
                        min2, loc);
+}
+
+// ------------------------------------------------------------------------------------ several lengths
+// shapelet_mindist for the window lengths m_0 < m_1 < ... < m_{n-1} of `lens` at once.  E does not
+// depend on m, and the walk of s(r, c) runs k ascending from +0, so its partial sum after m_l terms
+// is, bit for bit, the s of length m_l: one band (sized for m_max = m_{n-1}) and one walk per
+// (start, position) serve every length, each a snapshot compared against its own running
+// (min, loc).  The block table is that of m_0, which has the most starts; a start or position is
+// compared at length m_l only when its m_l rows lie within its clip (blk.r0 + r + m_l <= len_i,
+// c0 + c + m_l <= len_j), and as the lengths ascend the first that does not fit ends the walk, so
+// no E entry beyond the two clips is read.  The running pairs are kShpMaxLens scalars per thread
+// (the loops over l are fully unrolled: never an indexed array), the kShpSub threads of a start
+// are neighbouring lanes and merge on (bits, loc) by lane exchange, and length l's rows go to
+// rows[entry][l].out0 .. of min2 / loc.  LDS is dynamic: E [na][kShpND], xs [na][kShpDC + 1],
+// ys [nb][kShpDC + 1] with na = kShpTR + m_max - 1, nb = kShpTC + m_max - 1.
+static_assert(kShpSub <= 64 && (kShpSub & (kShpSub - 1)) == 0 && 64 % kShpSub == 0, "a start's threads share a wave");
+
+__global__ __launch_bounds__(kShpThreads) void shapelet_mindist_lengths(
+    const float* __restrict__ seq, const int64_t* __restrict__ off, int n_seq, int D, const ShpLens lens,
+    const ShpBlock* __restrict__ blocks, const ShpLenRows* __restrict__ rows, float* __restrict__ min2,
+    int32_t* __restrict__ loc) {
+    extern __shared__ float shp_lds[];
+    const int t = threadIdx.x, j = blockIdx.y;
+    const int m0 = lens.m[0], mx = lens.m[lens.n - 1];
+    const int na = kShpTR + mx - 1, nb = kShpTC + mx - 1;
+    float* E = shp_lds;
+    float* xs = E + na * kShpND;
+    float* ys = xs + na * (kShpDC + 1);
+    const ShpBlock blk = blocks[blockIdx.x];
+    const int64_t xo = off[blk.seq] + blk.r0;
+    const int xleft = (int)(off[blk.seq + 1] - xo);     // rows of the candidate clip from the entry's first start on
+    const int xrows = min(blk.nvalid + mx - 1, xleft);  // the window rows a valid output may read
+    const int64_t yo = off[j];
+    const int ylen = (int)(off[j + 1] - yo), P0 = ylen - m0 + 1;
+    const int r = t / kShpSub, sub = t % kShpSub;
+    uint32_t best[kShpMaxLens];
+    int bloc[kShpMaxLens];
+#pragma unroll
+    for (int l = 0; l < kShpMaxLens; ++l) {
+        best[l] = 0xffffffffu;
+        bloc[l] = 0;
+    }
+    for (int c0 = 0; c0 < P0; c0 += kShpTC) {
+        shp_fill_band(E, xs, ys, seq, xo, xrows, yo, ylen, c0, na, nb, D, t);
+        __syncthreads();
+        if (r < blk.nvalid) {
+            for (int c = sub; c < kShpTC && c0 + c < P0; c += kShpSub) {
+                const float* diag = E + r * kShpND + (c - r + kShpTR - 1);
+                const int fit = min(xleft - r, ylen - (c0 + c));  // the longest window that fits both clips here
+                float acc = 0.0f;
+                int k = 0;
+                bool go = true;
+#pragma unroll
+                for (int l = 0; l < kShpMaxLens; ++l) {
+                    go = go && l < lens.n && lens.m[l] <= fit;
+                    if (go) {
+                        for (; k < lens.m[l]; ++k) acc = acc + diag[k * kShpND];
+                        const uint32_t bits = __float_as_uint(acc);
+                        if (bits < best[l]) {
+                            best[l] = bits;
+                            bloc[l] = c0 + c;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();  // E is zeroed next
+    }
+#pragma unroll
+    for (int l = 0; l < kShpMaxLens; ++l) {
+        if (l < lens.n) {  // uniform: every lane of the wave exchanges
+            uint32_t b = best[l];
+            int bl = bloc[l];
+#pragma unroll
+            for (int s = 1; s < kShpSub; s <<= 1) {
+                const uint32_t ob = (uint32_t)__shfl_xor((int)b, s);
+                const int ol = __shfl_xor(bl, s);
+                if (ob < b || (ob == b && ol < bl)) {
+                    b = ob;
+                    bl = ol;
+                }
+            }
+            const ShpLenRows lr = rows[(size_t)blockIdx.x * lens.n + l];
+            if (sub == 0 && r < lr.nvalid) {
+                const size_t o = (size_t)(lr.out0 + r) * n_seq + j;
+                min2[o] = __uint_as_float(b);
+                loc[o] = bl;
+            }
+        }
+    }
+}
+
+size_t shapelet_lengths_lds_bytes(int m_max) {
+    const int na = kShpTR + m_max - 1, nb = kShpTC + m_max - 1;
+    return sizeof(float) * ((size_t)na * kShpND + (size_t)(na + nb) * (kShpDC + 1));
+}
+
+void launch_shapelet_mindist_lengths(const float* seq, const int64_t* off, int n_seq, int D, const ShpLens& lens,
+                                     const ShpBlock* blocks, const ShpLenRows* rows, int n_blocks, float* min2,
+                                     int32_t* loc, hipStream_t st) {
+    hipLaunchKernelGGL(shapelet_mindist_lengths, dim3(n_blocks, n_seq), dim3(kShpThreads),
+                       shapelet_lengths_lds_bytes(lens.m[lens.n - 1]), st, seq, off, n_seq, D, lens, blocks, rows, min2,
+                       loc);
 }
 
 // ------------------------------------------------------------------------------------ score

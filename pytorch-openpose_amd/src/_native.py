@@ -109,6 +109,8 @@ SIGNATURES = {
     "opose_sliding_distance": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _I]),
     "opose_shapelet_mindist": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _I]),
     "opose_shapelet_find": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I]),
+    "opose_shapelet_mindist_lengths": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _I]),
+    "opose_shapelet_find_lengths": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I]),
     "opose_debug_shapelet_score": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
 }
 EXPORTED = list(SIGNATURES)

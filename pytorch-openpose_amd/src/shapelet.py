@@ -151,6 +151,63 @@ def shapelet_find(seq, off, labels, m, max_cands=0, every=False, handle=None):
     return {"best": best, "loss": loss, "dis": dis, "locs": locs, "nums": nums, "losses": losses}
 
 
+def _lengths(m_lens) -> np.ndarray:
+    return np.ascontiguousarray([int(m) for m in m_lens], np.int32)
+
+
+def _empty(dev, like, shape, np_dtype):
+    import torch
+    if dev:
+        return torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=like.device)
+    return np.empty(shape, np_dtype)
+
+
+def shapelet_mindist_lengths(seq, off, m_lens, cand_seqs, handle=None):
+    """shapelet_mindist for the ascending window lengths m_lens in one pass over shared distances
+    (opose_shapelet_mindist_lengths): a list of (min2, loc) [n_cand_l, n_seq] per length, views of
+    the two output buffers."""
+    dev = _is_dev(seq)
+    off = np.ascontiguousarray(off, np.int64)
+    cs = np.ascontiguousarray(cand_seqs, np.int32)
+    ml = _lengths(m_lens)
+    n_seq = len(off) - 1
+    counts = [int(sum(max(int(off[i + 1] - off[i]) - int(m) + 1, 0) for i in cs if 0 <= i < n_seq)) for m in ml]
+    total = sum(counts)
+    h = handle or default_handle(seq.device.index if dev else 0)
+    min2, loc = _empty(dev, seq, (total, n_seq), np.float32), _empty(dev, seq, (total, n_seq), np.int32)
+    _run(h, dev, lib.opose_shapelet_mindist_lengths, _native._ptr(seq), off.ctypes.data, n_seq, seq.shape[1],
+         ml.ctypes.data, len(ml), cs.ctypes.data, len(cs), _native._ptr(min2), _native._ptr(loc),
+         _native.DEVICE_IO if dev else 0)
+    starts = np.concatenate(([0], np.cumsum(counts)))
+    return [(min2[a:b], loc[a:b]) for a, b in zip(starts[:-1], starts[1:])]
+
+
+def shapelet_find_lengths(seq, off, labels, m_lens, max_cands=0, every=False, handle=None):
+    """opose_shapelet_find_lengths on a ragged batch: a list, per length of m_lens, of the dict
+    shapelet_find returns (views of the call's output buffers).  Device inputs give device outputs."""
+    dev = _is_dev(seq)
+    off = np.ascontiguousarray(off, np.int64)
+    lab = np.ascontiguousarray(np.asarray(labels.cpu() if hasattr(labels, "cpu") else labels) != 0, np.uint8)
+    ml = _lengths(m_lens)
+    n_seq, n, nl = len(off) - 1, len(lab), len(ml)
+    counts = [int(sum(max(int(off[i + 1] - off[i]) - int(m) + 1, 0) for i in range(min(n, n_seq)) if lab[i]))
+              for m in ml]
+    total = sum(counts)
+    h = handle or default_handle(seq.device.index if dev else 0)
+    best, loss = _empty(dev, seq, (nl, 4), np.int32), _empty(dev, seq, (nl, 1), np.float64)
+    dis, locs = _empty(dev, seq, (nl, n_seq), np.float32), _empty(dev, seq, (nl, n_seq), np.int32)
+    nums = _empty(dev, seq, total, np.int32) if every else None
+    losses = _empty(dev, seq, total, np.float64) if every else None
+    _run(h, dev, lib.opose_shapelet_find_lengths, _native._ptr(seq), off.ctypes.data, n_seq, seq.shape[1],
+         ml.ctypes.data, nl, lab.ctypes.data, n, int(max_cands), _native._ptr(best), _native._ptr(loss),
+         _native._ptr(dis), _native._ptr(locs), _native._ptr(nums) if every else None,
+         _native._ptr(losses) if every else None, _native.DEVICE_IO if dev else 0)
+    starts = np.concatenate(([0], np.cumsum(counts)))
+    return [{"best": best[l], "loss": loss[l], "dis": dis[l], "locs": locs[l],
+             "nums": nums[starts[l]:starts[l + 1]] if every else None,
+             "losses": losses[starts[l]:starts[l + 1]] if every else None} for l in range(nl)]
+
+
 class ShapeletMatrixModel:
     """The reference's brute-force shapelet model: train() keeps the window of a positive clip whose
     distances to all clips separate the labels best."""
@@ -164,6 +221,24 @@ class ShapeletMatrixModel:
         mirror 'x-mirror' / 'y-mirror': the copies with the even / odd feature columns negated are
         appended (made with torch on the device); locs, dis and the boolean `mirrored` are then the
         chosen of each pair.  (The reference's ShapeletMatrixModel_LR fails in these modes.)"""
+        seq, off, n = self._batch(X, mirror)
+        return self._take(shapelet_find(seq, off, labels, m_len, max_cands, handle=self.handle), n, mirror)
+
+    def train_lengths(self, X, labels, m_lens, mirror=None, max_cands=0):
+        """train for every window length of m_lens (ascending) in one search over shared distances:
+        a list of models, one per length, each with m_len and the attributes train sets.  The
+        mirrored copies are made and uploaded once."""
+        seq, off, n = self._batch(X, mirror)
+        res = shapelet_find_lengths(seq, off, labels, m_lens, max_cands, handle=self.handle)
+        models = []
+        for m, r in zip(m_lens, res):
+            model = ShapeletMatrixModel(self.handle)._take(r, n, mirror)
+            model.m_len = int(m)
+            models.append(model)
+        return models
+
+    def _batch(self, X, mirror):
+        """(seq, off, clips): the ragged batch of X, with the mirrored copies appended when asked."""
         import torch
         seq, off, dev = _ragged(X)
         n = len(off) - 1
@@ -177,7 +252,10 @@ class ShapeletMatrixModel:
             sign[(0 if mirror == "x-mirror" else 1)::2] = -1
             seq = torch.cat((seq, seq * sign), dim=0)
             off = np.concatenate((off, off[1:] + off[-1]))
-        res = shapelet_find(seq, off, labels, m_len, max_cands, handle=self.handle)
+        return seq, off, n
+
+    def _take(self, res, n, mirror):
+        """The model's attributes from one length's search result over n clips."""
         host = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in res.items() if v is not None}
         best, dis, locs = host["best"], host["dis"], host["locs"]
         self.shapeindex, self.cand = int(best[0]), int(best[1])
@@ -193,3 +271,15 @@ class ShapeletMatrixModel:
         self.dis = dis[pick].astype(np.float64)
         self.locs = locs[pick].astype(np.int16)
         return self
+
+
+def brute_force_records(samples, labels, m_lens=range(15, 40, 2), mirror="x-mirror", max_cands=0, handle=None):
+    """The arrays FindShaplets_brute_force_ED (srcmx/shapeletlearning.py:190-214) writes per window
+    length, for every length of m_lens from one search and without the h5 file: {m: {"locs": int16
+    [positives], "dists": float32 [positives], "shapelet": int16 [1], "score": float32 [1]}}."""
+    lab = np.asarray(labels.cpu() if hasattr(labels, "cpu") else labels) != 0
+    m_lens = [int(m) for m in m_lens]
+    models = ShapeletMatrixModel(handle).train_lengths(samples, lab, m_lens, mirror=mirror, max_cands=max_cands)
+    return {m: {"locs": model.locs[lab].astype(np.int16), "dists": model.dis[lab].astype(np.float32),
+                "shapelet": np.array([model.shapeindex]).astype(np.int16),
+                "score": np.array([model.score]).astype(np.float32)} for m, model in zip(m_lens, models)}
