@@ -640,6 +640,30 @@ int opose_debug_limb_greedy(opose_t* h, const double* score, const int32_t* part
  * have for the kernel to stage them all at once; beyond, it stages limb by limb */
 int opose_debug_assemble(opose_t* h, void* records, const int32_t* part_cnt, const int32_t* conn_i,
                          const int32_t* conn_j, const double* conn_s, const int32_t* conn_cnt, int N, int* stage);
+/* The exact mode's peak finder and heat average, one launch each (own buffers, synchronous), through
+ * the launchers Body's and Hand's post paths use.
+ *
+ * src/body.py:70-94 on NP maps [NP,H,W], float32 (is_f32) or float64 (gauss_nms_wide):
+ * gaussian_filter(map, 3), peaks > thre that are >= their 4 neighbours (zero outside the map) ->
+ * cnt [NP] (every peak, may pass cap), list [NP,cap] (y * W + x of the first cap peaks, in no
+ * order; unused slots -1) and score [NP,cap] (the unsmoothed map at the peak; unused slots 0) */
+int opose_debug_gauss_nms(opose_t* h, const void* maps, int is_f32, int NP, int H, int W, double thre, int cap,
+                          int32_t* cnt, int32_t* list, double* score);
+/* The same with the single scale's cv2.resize fused in (gauss_nms_resize, src/body.py:57,70-94):
+ * channels [coff, coff + P) of the x8 maps mid [N,Cm,Hs,Ws] float32 resized to H x W with source
+ * steps 1 / (H / Hs), 1 / (W / Ws), then as above on the N * P float32 maps: cnt [N * P], list /
+ * score [N * P,cap].  OPOSE_E_ARG without a launch for a geometry the kernel does not take (an
+ * identity resize, or a vertical source step above 34 / 55) */
+int opose_debug_gauss_nms_resize(opose_t* h, const float* mid, int N, int Cm, int coff, int P, int Hs, int Ws, int H,
+                                 int W, double thre, int cap, int32_t* cnt, int32_t* list, double* score);
+/* src/body.py:51-67 / src/hand.py:43-56, the heat average of n scales: channels [coff, coff + C) of
+ * mids[s] [N,Cm,Hs[s],Ws[s]] float32, each resized to H x W (copied where it has that size), divided
+ * by n in float32 and added in scale order from 0.0 in float64 -> avg [N * C,H,W] float64.
+ * one_launch 1: every scale in one launch (heat_full_scales), OPOSE_E_ARG without a launch where
+ * that form does not take the scales (more than 8, or a resizing scale with a vertical source step
+ * above 2.4375); 0: a launch per scale (n <= 16), accumulating from the second on */
+int opose_debug_heat_scales(opose_t* h, int n, const float* const* mids, const int* Hs, const int* Ws, int N, int Cm,
+                            int coff, int C, int H, int W, int one_launch, double* avg);
 /* The hand extraction kernels (srcmx/Batch_model.py:86-102, srcmx/Batch_motion_Estimation.py:44-58),
  * each through the call opose_batch_hand_extract makes, on host arrays and synchronously.
  * (hand_boxes needs no hook: opose_batch_hand_boxes takes the poses.)

@@ -989,6 +989,104 @@ int opose_debug_assemble(opose_t* h, void* records, const int32_t* part_cnt, con
     return OPOSE_OK;
 }
 
+// ---- the exact mode's peak finder and heat average one launch at a time
+// (tests/test_gpu_peak_stages.py), modelled on opose_debug_blur5_nms: own buffers, cnt zeroed,
+// list preset to -1 and score to 0, one launch, copied back and synchronised
+struct DebugPeaks {
+    DevBuf cb, lb, sb;
+    int NP;
+    size_t nl;
+    int *cnt, *list;
+    double* score;
+    DebugPeaks(opose_ctx* h, int NP_, int cap) : NP(NP_), nl((size_t)NP_ * cap) {
+        cnt = cb.ensure<int>((size_t)NP, h->stream);
+        list = lb.ensure<int>(nl, h->stream);
+        score = sb.ensure<double>(nl, h->stream);
+        OPOSE_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * NP, h->stream));
+        OPOSE_HIP_CHECK(hipMemsetAsync(list, 0xff, sizeof(int) * nl, h->stream));  // unused slots: -1
+        OPOSE_HIP_CHECK(hipMemsetAsync(score, 0, sizeof(double) * nl, h->stream));
+    }
+    void fetch(opose_ctx* h, int32_t* c, int32_t* l, double* s) {
+        to_host(h, c, cnt, (size_t)NP);
+        to_host(h, l, list, nl);
+        to_host(h, s, score, nl);
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    }
+};
+
+int opose_debug_gauss_nms(opose_t* h, const void* maps, int is_f32, int NP, int H, int W, double thre, int cap,
+                          int32_t* cnt, int32_t* list, double* score) {
+    if (!h || !maps || !cnt || !list || !score || NP <= 0 || H <= 0 || W <= 0 || cap <= 0) return OPOSE_E_ARG;
+    if ((int64_t)H * W > 0x7fffffff) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        DevBuf mb;
+        const size_t bytes = (size_t)NP * H * W * (is_f32 ? 4 : 8);
+        const uint8_t* md = to_device(h, mb, static_cast<const uint8_t*>(maps), bytes);
+        DebugPeaks out(h, NP, cap);
+        launch_gauss_nms(md, is_f32 != 0, NP, H, W, thre, cap, out.cnt, out.list, out.score, h->stream);
+        out.fetch(h, cnt, list, score);
+    });
+    return OPOSE_OK;
+}
+
+int opose_debug_gauss_nms_resize(opose_t* h, const float* mid, int N, int Cm, int coff, int P, int Hs, int Ws, int H,
+                                 int W, double thre, int cap, int32_t* cnt, int32_t* list, double* score) {
+    if (!h || !mid || !cnt || !list || !score || N <= 0 || P <= 0 || coff < 0 || coff + P > Cm) return OPOSE_E_ARG;
+    if (Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0 || cap <= 0 || (int64_t)H * W > 0x7fffffff) return OPOSE_E_ARG;
+    const double sy = 1.0 / ((double)H / Hs), sx = 1.0 / ((double)W / Ws);  // as geom_from_pads
+    if (!gauss_nms_resize_fits(Hs, Ws, H, W, sy)) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        DevBuf mb;
+        const float* md = to_device(h, mb, mid, (size_t)N * Cm * Hs * Ws);
+        DebugPeaks out(h, N * P, cap);
+        launch_gauss_nms_resize(md, Cm, coff, P, N, Hs, Ws, H, W, sy, sx, thre, cap, out.cnt, out.list, out.score,
+                                h->stream);
+        out.fetch(h, cnt, list, score);
+    });
+    return OPOSE_OK;
+}
+
+int opose_debug_heat_scales(opose_t* h, int n, const float* const* mids, const int* Hs, const int* Ws, int N, int Cm,
+                            int coff, int C, int H, int W, int one_launch, double* avg) {
+    constexpr int kMost = 16;  // scales of the per-scale form (the one-launch form: kHeatScales)
+    if (!h || !mids || !Hs || !Ws || !avg || n < 1 || n > kMost || N <= 0 || C <= 0 || coff < 0 || coff + C > Cm)
+        return OPOSE_E_ARG;
+    if (H <= 0 || W <= 0) return OPOSE_E_ARG;
+    for (int s = 0; s < n; ++s)
+        if (!mids[s] || Hs[s] <= 0 || Ws[s] <= 0) return OPOSE_E_ARG;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        DevBuf mb[kMost], ab;
+        HeatScales S{};
+        S.n = n;
+        S.ns = (float)n;
+        double sy[kMost], sx[kMost];
+        for (int s = 0; s < n; ++s) {
+            sy[s] = 1.0 / ((double)H / Hs[s]);  // as geom_from_pads
+            sx[s] = 1.0 / ((double)W / Ws[s]);
+            if (s < kHeatScales) S.s[s] = HeatScale{nullptr, Cm, coff, Hs[s], Ws[s], sy[s], sx[s]};
+        }
+        if (one_launch && !heat_full_scales_fits(S, H, W)) return OPOSE_E_ARG;
+        const float* md[kMost];
+        for (int s = 0; s < n; ++s) md[s] = to_device(h, mb[s], mids[s], (size_t)N * Cm * Hs[s] * Ws[s]);
+        const size_t na = (size_t)N * C * H * W;
+        double* ad = ab.ensure<double>(na, h->stream);
+        OPOSE_HIP_CHECK(hipMemsetAsync(ad, kDebugFill, na * 8, h->stream));
+        if (one_launch) {
+            for (int s = 0; s < n; ++s) S.s[s].mid = md[s];
+            launch_heat_full_scales(S, N, C, H, W, ad, h->stream);
+        } else {
+            for (int s = 0; s < n; ++s)
+                launch_heat_full(md[s], Cm, coff, C, N, Hs[s], Ws[s], H, W, sy[s], sx[s], n, s > 0, ad, h->stream);
+        }
+        to_host(h, avg, ad, na);
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    });
+    return OPOSE_OK;
+}
+
 // ---- the hand extraction kernels one at a time (tests/test_gpu_hand_stages.py): the calls
 // opose_batch_hand_extract makes, on host arrays.  (hand_boxes: opose_batch_hand_boxes.)
 int opose_debug_hand_crops(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,

@@ -59,7 +59,8 @@ def test_null_handle_is_an_argument_error_everywhere():
             "opose_debug_batch_hand_label", "opose_debug_conv_segs", "opose_debug_chain",
             "opose_debug_conv1", "opose_debug_peaks_finalize", "opose_debug_paf_score",
             "opose_debug_limb_greedy", "opose_debug_assemble", "opose_debug_hand_crops",
-            "opose_debug_hand_backmap"} <= set(checked)
+            "opose_debug_hand_backmap", "opose_debug_gauss_nms", "opose_debug_gauss_nms_resize",
+            "opose_debug_heat_scales"} <= set(checked)
 
 
 def test_default_params_are_reference_constants():
