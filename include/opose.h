@@ -34,6 +34,8 @@
  *                                  97-209                    opose_shapelet_mindist (first stage)
  *   ShapeletsFinding.train's       srcmx/shapeletlearning    opose_shapelet_find_lengths;
  *   m_len loop                     .py:123-175               opose_shapelet_mindist_lengths
+ *   DataAugmentation.              srcmx/DataAugmentation    opose_shapelet_scan;
+ *   AugmentateOneShapelet          .py:78-153                opose_debug_shapelet_pick (the hit walk)
  *
  * Conventions: plain pointers and sizes only; 0 = OK, negative = error (see opose_status).
  * Host pointers are caller-owned and read-only; the library copies them. A handle owns one
@@ -480,6 +482,47 @@ int opose_shapelet_find_lengths(opose_t* h, const float* seq, const int64_t* off
                                 int max_cands, int32_t* best, double* best_loss, float* dis, int32_t* locs,
                                 int32_t* cand_num, double* cand_loss, int flags);
 
+/* Every occurrence of n_pat patterns in n_seq whole streams (DataAugmentation.AugmentateOneShapelet,
+ * srcmx/DataAugmentation.py:106-150, for all patterns and videos in one call).
+ *
+ * pat float32 [M][D], ragged by pat_off int64 [n_pat + 1] (host memory): pattern p is rows pat_off[p]
+ * .. pat_off[p + 1] - 1, m_p = 1 .. 128 of them; pat is device memory with OPOSE_IN_DEVICE, as seq.
+ * sigma float32 [n_pat], host memory.  seq / off: a ragged batch as above, except that a stream may
+ * have any length >= 0: position c of stream j exists for pattern p when c + m_p <= len_j, and a
+ * stream shorter than the pattern, or empty, has no positions and is no error.
+ *
+ * The rule.  dist_p(j, c) is the distance rule above (fp32, one rounding per operation, no fused
+ * multiply-add; e over d ascending from +0, s over k ascending from +0, dist = sqrt(s) correctly
+ * rounded): bit for bit what opose_sliding_distance returns for that pattern and stream.  A position
+ * is a hit when dist < sigma_p, a strict float32 compare on the square root; a NaN or non-positive
+ * sigma gives no hits.  The occurrences of a pair (p, j) come from one walk over its hits, c
+ * ascending, with the state (pre, last entry):
+ *   the first hit:                                 append (c, dist), pre = c
+ *   a later hit with 2 (c - pre) > m_p:            append (c, dist), pre = c
+ *   else, dist < the last entry's dist (strict):   the last entry becomes (c, dist), pre = c
+ *   else:                                          nothing; pre stays
+ * (the reference's idex - preidx > m / 2 with true division).  pre moves on a replacement, so a run
+ * of falling distances drags its entry along and a run of rising ones does not, as in the
+ * reference.  tests/shapelet_scan_cases.py states the rule in NumPy.
+ *
+ * occ_off int64 [n_pat * n_seq + 1], pattern-major: pair (p, j)'s entries are occ_off[p * n_seq + j]
+ * .. occ_off[p * n_seq + j + 1] - 1 of occ_pos int32 (the position within its stream) and occ_dist
+ * float32.  occ_off is always written in full, so its last value is the total; of the entries the
+ * first min(total, cap) are written.  With host outputs the call returns OPOSE_E_CAPACITY when the
+ * total exceeds cap (occ_off is valid: the caller can size a retry); with OPOSE_OUT_DEVICE the call
+ * is asynchronous, returns OPOSE_OK, and the caller reads the total.
+ *
+ * The patterns are processed in chunks of max_pats (0: the library's default) consecutive patterns,
+ * which bounds the workspace (a chunk's distances are max_pats rows of L floats); the running total
+ * stays on the device and the result does not depend on the chunking.  Checked before anything is
+ * launched: OPOSE_E_ARG for a null handle or pointer, n_pat < 1, n_seq < 1, D < 1, max_pats < 0,
+ * cap < 0, offsets that do not start at 0 or that decrease, or a pattern of 0 rows; OPOSE_E_SHAPE
+ * for n_pat > 4096, n_pat * n_seq > 2^22, n_seq > 4096, D > 1024, a pattern of more than 128 rows
+ * or L >= 2^31. */
+int opose_shapelet_scan(opose_t* h, const float* pat, const int64_t* pat_off, int n_pat, const float* sigma,
+                        const float* seq, const int64_t* off, int n_seq, int D, int max_pats,
+                        int64_t* occ_off, int32_t* occ_pos, float* occ_dist, int64_t cap, int flags);
+
 /* Hand on N crops uint8 [H][W][3] (util.handDetect gives squares): peaks [N][21][3]
  * (x, y, score), found [N][21] (0 = part missing, the reference's [0,0,0] row). */
 int opose_hand_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
@@ -696,6 +739,12 @@ int opose_debug_draw_prims(opose_t* h, const void* src, int N, int joints, int H
  * the winning row, its num, n_cand; win_loss its loss. */
 int opose_debug_shapelet_score(opose_t* h, const float* min2, int n_cand, int n_seq, const uint8_t* labels,
                                int n_labels, int32_t* num, double* loss, int32_t* winner, double* win_loss);
+/* The second stage of opose_shapelet_scan alone, for one pattern of m rows, on given host arrays:
+ * dist float32 [L], one value per row of the ragged batch off [n_seq + 1] (the values at a stream's
+ * last m - 1 rows, where no position exists, are ignored).  The hits are dist < sigma; occ_off
+ * [n_seq + 1], occ_pos, occ_dist, cap and the return value as opose_shapelet_scan with host outputs. */
+int opose_debug_shapelet_pick(opose_t* h, const float* dist, const int64_t* off, int n_seq, int m, float sigma,
+                              int64_t* occ_off, int32_t* occ_pos, float* occ_dist, int64_t cap);
 
 #ifdef __cplusplus
 }

@@ -433,6 +433,9 @@ struct opose_ctx {
     // per-length tables handed to the selection
     opose::DevBuf shp_seq, shp_off, shp_labels, shp_in, shp_blocks, shp_min2, shp_loc, shp_num, shp_loss, shp_best,
         shp_carry, shp_out, shp_lrows, shp_sel;
+    // opose_shapelet_scan: the pattern table and window lengths, a chunk's distance rows and hit
+    // masks, its per-pair counts, the running total, and the staged occurrence outputs
+    opose::DevBuf scan_pats, scan_m, scan_dist, scan_mask, scan_counts, scan_total, scan_off, scan_pos, scan_odist;
     // opose_batch_hand_extract cuts its 2N crops into chunks the conv kernels can address (as
     // opose_hand_infer_crops does); OPOSE_EXTRACT_CHUNK=n at handle creation: n crops per chunk
     // instead (tests/test_gpu_hand_extract.py runs a small batch in two chunks)

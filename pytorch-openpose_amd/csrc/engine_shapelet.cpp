@@ -1,5 +1,6 @@
 // engine_shapelet.cpp — the shapelet search entry points: validation of the ragged batch, the block
-// table of the candidate starts, chunking, and the launches of shapelet.hip.
+// table of the candidate starts, chunking, and the launches of shapelet.hip; and the scan of whole
+// streams for many patterns (its pattern table, chunks and occurrence outputs).
 #include "engine.h"
 
 namespace opose {
@@ -517,4 +518,179 @@ int opose_shapelet_find_lengths(opose_t* h, const float* seq, const int64_t* off
         h->prof_drain();
     });
     return OPOSE_OK;
+}
+
+// ------------------------------------------------------------------------------------ scan
+namespace opose {
+
+// A ragged batch whose sequences may have any length >= 0 (the streams of a scan; the patterns,
+// which the caller checks for empty ones): n >= 1 is the caller's.  OPOSE_E_ARG unless off starts
+// at 0 and never decreases.
+static int scan_offsets_check(opose_ctx* h, const int64_t* off, int n) {
+    if (off[0] != 0) {
+        h->err = "shapelet scan: offsets must start at 0";
+        return OPOSE_E_ARG;
+    }
+    for (int j = 0; j < n; ++j)
+        if (off[j + 1] < off[j]) {
+            h->err = "shapelet scan: offsets must not decrease";
+            return OPOSE_E_ARG;
+        }
+    return OPOSE_OK;
+}
+
+// The pick stage of one chunk: count, offsets, write.  pair0: the chunk's first pair in occ_off.
+static void run_scan_pick(opose_ctx* h, const float* dist, const uint64_t* mask, const int32_t* m_slot,
+                          const int64_t* off, int n_seq, int64_t L, int n_pairs, bool first, int32_t* counts,
+                          int64_t* running, int64_t* occ_off, int32_t* occ_pos, float* occ_dist, int64_t cap) {
+    for (int pass = 0; pass < 2; ++pass) {
+        ProfEntry pe;
+        h->prof_begin(pe, "shapelet_scan_pick", 0, (double)n_pairs * 16.0 + (double)(n_pairs / n_seq) * (double)L / 8.0);
+        launch_shapelet_scan_pick(dist, mask, m_slot, off, n_seq, L, n_pairs, counts, occ_off, occ_pos, occ_dist, cap,
+                                  pass == 1, h->stream);
+        h->prof_end(pe);
+        if (pass == 0) launch_shapelet_scan_offsets(counts, n_pairs, first, running, occ_off, h->stream);
+    }
+}
+
+// the occurrence outputs of a call with host outputs: occ_off in full, then the first
+// min(total, cap) entries; OPOSE_E_CAPACITY when the total exceeds cap
+static int scan_copy_out(opose_ctx* h, int64_t n_pairs, const int64_t* offd, const int32_t* posd, const float* distd,
+                         int64_t* occ_off, int32_t* occ_pos, float* occ_dist, int64_t cap) {
+    OPOSE_HIP_CHECK(hipMemcpyAsync(occ_off, offd, (size_t)(n_pairs + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    const int64_t total = occ_off[n_pairs], n = std::min(total, cap);
+    if (n > 0) {
+        OPOSE_HIP_CHECK(hipMemcpyAsync(occ_pos, posd, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(occ_dist, distd, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    }
+    if (total > cap) {
+        h->err = "shapelet scan: more occurrences than cap (occ_off holds the counts)";
+        return OPOSE_E_CAPACITY;
+    }
+    return OPOSE_OK;
+}
+
+}  // namespace opose
+
+int opose_shapelet_scan(opose_t* h, const float* pat, const int64_t* pat_off, int n_pat, const float* sigma,
+                        const float* seq, const int64_t* off, int n_seq, int D, int max_pats, int64_t* occ_off,
+                        int32_t* occ_pos, float* occ_dist, int64_t cap, int flags) {
+    if (!h || !pat || !pat_off || !sigma || !seq || !off || !occ_off) return OPOSE_E_ARG;
+    if (n_pat < 1 || n_seq < 1 || D < 1 || max_pats < 0 || cap < 0) return OPOSE_E_ARG;
+    if (cap > 0 && (!occ_pos || !occ_dist)) return OPOSE_E_ARG;
+    if (n_pat > kScanMaxPat || n_seq > kShpMaxSeq || D > kShpMaxD || (int64_t)n_pat * n_seq > kScanMaxPairs) {
+        h->err = "shapelet scan: patterns, streams, pairs or D beyond the supported limit";
+        return OPOSE_E_SHAPE;
+    }
+    if (const int rc = scan_offsets_check(h, pat_off, n_pat)) return rc;
+    if (const int rc = scan_offsets_check(h, off, n_seq)) return rc;
+    int m_max = 0;
+    for (int p = 0; p < n_pat; ++p) {
+        if (pat_off[p + 1] == pat_off[p]) {
+            h->err = "shapelet scan: a pattern of 0 rows";
+            return OPOSE_E_ARG;
+        }
+        m_max = (int)std::min<int64_t>(std::max<int64_t>(m_max, pat_off[p + 1] - pat_off[p]), kShpMaxM + 1);
+    }
+    if (m_max > kShpMaxM || off[n_seq] > kShpMaxRows) {
+        h->err = "shapelet scan: a pattern or the batch beyond the supported limit";
+        return OPOSE_E_SHAPE;
+    }
+    int status = OPOSE_OK;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const bool id = flags & OPOSE_IN_DEVICE, od = flags & OPOSE_OUT_DEVICE;
+        const int64_t L = off[n_seq], nwords = (L + 63) / 64, n_pairs = (int64_t)n_pat * n_seq;
+        int chunk = max_pats;
+        if (!chunk)  // the default, halved while the distance rows of a chunk exceed 1 GiB
+            for (chunk = kScanDefaultPats; chunk > 1 && (int64_t)chunk * L > (int64_t)1 << 28;) chunk /= 2;
+        chunk = std::min(chunk, n_pat);
+        const bool lds = shapelet_scan_lds_bytes(m_max, D) <= (size_t)kScanLdsBytes;
+        // per chunk of consecutive patterns: its table entries, sorted by length (then by pattern),
+        // filled up to whole groups with copies of the last that write nothing
+        struct Chunk {
+            int p0, np, e0, groups, m_max;
+            double rows;  // the sum of the window lengths
+        };
+        std::vector<Chunk> chunks;
+        std::vector<ScanPat> table;
+        std::vector<int32_t> m_all(n_pat);
+        for (int p = 0; p < n_pat; ++p) m_all[p] = (int32_t)(pat_off[p + 1] - pat_off[p]);
+        for (int p0 = 0; p0 < n_pat; p0 += chunk) {
+            const int np = std::min(chunk, n_pat - p0);
+            std::vector<int> order(np);
+            for (int i = 0; i < np; ++i) order[i] = p0 + i;
+            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return m_all[a] < m_all[b]; });
+            Chunk c{p0, np, (int)table.size(), (np + kScanPG - 1) / kScanPG, m_all[order[np - 1]], 0.0};
+            for (int i = 0; i < c.groups * kScanPG; ++i) {
+                const int p = order[std::min(i, np - 1)];
+                table.push_back(ScanPat{pat_off[p], m_all[p], i < np ? p - p0 : -1, sigma[p], 0});
+                if (i < np) c.rows += m_all[p];
+            }
+            chunks.push_back(c);
+        }
+        const float* sd = L ? shp_stage(h, h->shp_seq, seq, (size_t)L * D, id) : nullptr;
+        const float* pd = shp_stage(h, h->shp_in, pat, (size_t)pat_off[n_pat] * D, id);
+        const int64_t* offd = shp_stage(h, h->shp_off, off, (size_t)n_seq + 1, false);
+        float* dd = h->scan_dist.ensure<float>((size_t)chunk * std::max<int64_t>(L, 1), h->stream);
+        uint64_t* mk = h->scan_mask.ensure<uint64_t>((size_t)chunk * std::max<int64_t>(nwords, 1), h->stream);
+        int32_t* counts = h->scan_counts.ensure<int32_t>((size_t)chunk * n_seq, h->stream);
+        int64_t* running = h->scan_total.ensure<int64_t>(1, h->stream);
+        int64_t* ofd = od ? occ_off : h->scan_off.ensure<int64_t>((size_t)n_pairs + 1, h->stream);
+        int32_t* posd = od ? occ_pos : h->scan_pos.ensure<int32_t>((size_t)std::max<int64_t>(cap, 1), h->stream);
+        float* odd = od ? occ_dist : h->scan_odist.ensure<float>((size_t)std::max<int64_t>(cap, 1), h->stream);
+        const ScanPat* td = shp_upload(h, h->scan_pats, table);
+        const int32_t* md = shp_upload(h, h->scan_m, m_all);
+        for (size_t ci = 0; ci < chunks.size(); ++ci) {
+            const Chunk& c = chunks[ci];
+            if (L) {
+                ProfEntry pe;
+                h->prof_begin(pe, "shapelet_scan_dist", 3.0 * c.rows * (double)L * D,
+                              4.0 * c.groups * (double)L * D + 4.0 * c.np * (double)L + 8.0 * c.np * (double)nwords);
+                launch_shapelet_scan_dist(pd, td + c.e0, c.groups, m_max, lds, sd, offd, n_seq, L, D, dd, mk, h->stream);
+                h->prof_end(pe);
+            }
+            run_scan_pick(h, dd, mk, md + c.p0, offd, n_seq, L, c.np * n_seq, ci == 0, counts, running,
+                          ofd + (size_t)c.p0 * n_seq, posd, odd, cap);
+        }
+        if (!od) status = scan_copy_out(h, n_pairs, ofd, posd, odd, occ_off, occ_pos, occ_dist, cap);
+        h->prof_drain();
+    });
+    return status;
+}
+
+int opose_debug_shapelet_pick(opose_t* h, const float* dist, const int64_t* off, int n_seq, int m, float sigma,
+                              int64_t* occ_off, int32_t* occ_pos, float* occ_dist, int64_t cap) {
+    if (!h || !dist || !off || !occ_off || n_seq < 1 || m < 1 || cap < 0) return OPOSE_E_ARG;
+    if (cap > 0 && (!occ_pos || !occ_dist)) return OPOSE_E_ARG;
+    if (n_seq > kShpMaxSeq || m > kShpMaxM) return OPOSE_E_SHAPE;
+    if (const int rc = scan_offsets_check(h, off, n_seq)) return rc;
+    if (off[n_seq] > kShpMaxRows) return OPOSE_E_SHAPE;
+    int status = OPOSE_OK;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const int64_t L = off[n_seq], nwords = (L + 63) / 64;
+        DevBuf db, mb, ob, sb, cb, rb, fb, pb, eb;
+        float* dd = db.ensure<float>((size_t)std::max<int64_t>(L, 1), h->stream);
+        uint64_t* mk = mb.ensure<uint64_t>((size_t)std::max<int64_t>(nwords, 1), h->stream);
+        int64_t* offd = ob.ensure<int64_t>((size_t)n_seq + 1, h->stream);
+        int32_t* counts = cb.ensure<int32_t>((size_t)n_seq, h->stream);
+        int64_t* running = rb.ensure<int64_t>(1, h->stream);
+        int64_t* ofd = fb.ensure<int64_t>((size_t)n_seq + 1, h->stream);
+        int32_t* posd = pb.ensure<int32_t>((size_t)std::max<int64_t>(cap, 1), h->stream);
+        float* odd = eb.ensure<float>((size_t)std::max<int64_t>(cap, 1), h->stream);
+        const std::vector<int32_t> one{m};
+        const int32_t* md = shp_upload(h, sb, one);
+        OPOSE_HIP_CHECK(hipMemcpyAsync(offd, off, ((size_t)n_seq + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        if (L) {
+            OPOSE_HIP_CHECK(hipMemcpyAsync(dd, dist, (size_t)L * 4, hipMemcpyHostToDevice, h->stream));
+            launch_shapelet_scan_mask(dd, offd, n_seq, L, m, sigma, mk, h->stream);
+        }
+        run_scan_pick(h, dd, mk, md, offd, n_seq, L, n_seq, true, counts, running, ofd, posd, odd, cap);
+        status = scan_copy_out(h, n_seq, ofd, posd, odd, occ_off, occ_pos, occ_dist, cap);
+        h->prof_drain();
+    });
+    return status;
 }

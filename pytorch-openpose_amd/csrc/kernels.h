@@ -200,6 +200,24 @@ void launch_shapelet_score(const float* min2, int n_cand, int n_seq, int n_label
 void launch_shapelet_select(const int32_t* num, const double* loss, int n_cand, const ShpBlock* blocks, int n_blocks,
                             const float* min2, const int32_t* loc, int n_seq, int first, int32_t* best,
                             double* best_loss, float* dis, int32_t* locs, hipStream_t st);
+// The scan (opose_shapelet_scan), per chunk of patterns.  pats: n_groups * kScanPG table entries,
+// each group sorted by length (m_max: the longest of the table); dist [slots][L] and mask [slots]
+// [ceil(L / 64)] are the chunk's workspace.  lds: stage the stream tiles in LDS, which needs
+// shapelet_scan_lds_bytes(m_max, D) <= kScanLdsBytes.  L >= 1.
+size_t shapelet_scan_lds_bytes(int m_max, int D);
+void launch_shapelet_scan_dist(const float* pat, const ScanPat* pats, int n_groups, int m_max, bool lds,
+                               const float* seq, const int64_t* off, int n_seq, int64_t L, int D, float* dist,
+                               uint64_t* mask, hipStream_t st);
+void launch_shapelet_scan_mask(const float* dist, const int64_t* off, int n_seq, int64_t L, int m, float sigma,
+                               uint64_t* mask, hipStream_t st);
+// pairs (slot, stream), slot-major; m_slot [slots]: the window length of each slot.  write false:
+// counts [n_pairs]; true: the entries from occ_off[pair] on, those at or past cap dropped
+void launch_shapelet_scan_pick(const float* dist, const uint64_t* mask, const int32_t* m_slot, const int64_t* off,
+                               int n_seq, int64_t L, int n_pairs, int32_t* counts, const int64_t* occ_off,
+                               int32_t* occ_pos, float* occ_dist, int64_t cap, bool write, hipStream_t st);
+// occ_off [n + 1] of a chunk from its counts, continuing the running total kept at *running
+void launch_shapelet_scan_offsets(const int32_t* counts, int n, bool first, int64_t* running, int64_t* occ_off,
+                                  hipStream_t st);
 
 // post.hip
 void launch_gauss_nms(const void* avg, bool f32, int NP, int H, int W, double thre, int cap, int* cnt, int* list,

@@ -25,6 +25,23 @@ constexpr int kShpDefaultCands = 2048;
 // motion_features: rows per fill block (the carry of the forward fill crosses these)
 constexpr int kFeatRows = 64;
 constexpr int kFeatThreads = 256;
+// opose_shapelet_scan: patterns and (pattern, stream) pairs of one call
+constexpr int kScanMaxPat = 4096;
+constexpr int kScanMaxPairs = 4194304;
+// shapelet_scan_dist: a workgroup takes kScanTC consecutive rows of the batch as positions against
+// a group of kScanPG patterns (sorted by length); its kScanThreads / kScanTC thread sets share the
+// group's patterns, kScanPT each.  The stream tile goes to LDS when it fits kScanLdsBytes (two
+// workgroups per CU), else the rows are read from global memory.
+constexpr int kScanTC = 128;
+constexpr int kScanPG = 16;
+constexpr int kScanThreads = 256;
+constexpr int kScanPT = kScanPG / (kScanThreads / kScanTC);  // patterns a thread accumulates
+constexpr int kScanLdsBytes = 81920;
+// shapelet_scan_pick: one wave per pair, kScanPickPairs pairs per workgroup, 64 mask words a step
+constexpr int kScanPickPairs = 4;
+// opose_shapelet_scan: patterns per chunk when the caller passes max_pats = 0 (the distance
+// workspace is that many rows of L floats: 256 MB at L = 10^6)
+constexpr int kScanDefaultPats = 64;
 
 // kShpTR consecutive candidate starts r0 .. r0 + nvalid - 1 of sequence `seq`; out0: the row of the
 // launch's output that start r0 writes
@@ -41,6 +58,16 @@ struct ShpLens {
 // and the output row the first of them writes
 struct ShpLenRows {
     int32_t out0, nvalid;
+};
+
+// shapelet_scan_dist: one pattern of a chunk's table (sorted by length, groups of kScanPG; a
+// group's missing entries repeat its last pattern with slot -1).  row0: the pattern's first row in
+// pat; slot: its row of the chunk's dist / mask workspace (the caller's order), -1: writes nothing
+struct ScanPat {
+    int64_t row0;
+    int32_t m, slot;
+    float sigma;
+    int32_t pad;
 };
 
 }  // namespace opose

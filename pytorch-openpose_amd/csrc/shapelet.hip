@@ -10,6 +10,8 @@
 //    per-sample torch.min                                                 => shapelet_mindist
 //  * srcmx/shapeletmodel.py:157-209      Bipartition_score, the loss and the best-candidate update
 //                                                                         => shapelet_score, shapelet_select
+//  * srcmx/DataAugmentation.py:106-150   AugmentateOneShapelet's sliding distances, hits below
+//    sigma and the thinning of neighbouring hits   => shapelet_scan_dist, shapelet_scan_pick
 //
 // The distance rule (fp32, one rounding per operation; this file is built without FMA contraction):
 //   e(a, b) = sum over d ascending of (x[a,d] - y[b,d])^2, from +0
@@ -540,6 +542,256 @@ void launch_shapelet_select(const int32_t* num, const double* loss, int n_cand, 
                             double* best_loss, float* dis, int32_t* locs, hipStream_t st) {
     hipLaunchKernelGGL(shapelet_select, dim3(1), dim3(kShpThreads), 0, st, num, loss, n_cand, blocks, n_blocks, min2, loc,
                        n_seq, first, best, best_loss, dis, locs);
+}
+
+// ------------------------------------------------------------------------------------ scan
+// Every occurrence of many patterns in whole streams (srcmx/DataAugmentation.py:106-150).
+//
+// shapelet_scan_dist, workgroup (tile of kScanTC consecutive rows of the batch, group of kScanPG
+// patterns of the chunk's table): every row g of the tile is a position -- c = g - off[j] of its
+// stream j -- of every pattern of the group, and
+//   dist[slot][g] = sqrt(s) where the position exists (g + m <= off[j + 1]),
+//   mask[slot][g / 64] bit g % 64 = the position exists and dist < sigma (float32, strict),
+// under the distance rule above: e over d ascending from +0, s over k ascending from +0.  Thread
+// t takes position t % kScanTC against the kScanPT patterns of its thread set t / kScanTC, which
+// is uniform over a wave: the pattern values are scalar loads.  The group is sorted by length; a
+// thread walks k to its set's longest window and a pattern's s stops taking terms after its own
+// m (rows past a pattern's end repeat its last row, and their e is dropped), so no row outside pat
+// is read.  kLds: the tile's kScanTC + (group's longest m) - 1 rows are staged once into LDS (row
+// stride D | 1: lanes read distinct banks) and serve every pattern of the group; else a thread
+// reads its rows from global memory.  Rows past L read as +0 (LDS) or repeat row L - 1 (global):
+// only positions that do not exist see them.  A wave's 64 positions are one mask word, written
+// whole by lane 0 from a ballot: every word of the mask is written.  No atomics.
+template <bool kLds>
+__global__ __launch_bounds__(kScanThreads) void shapelet_scan_dist(
+    const float* __restrict__ pat, const ScanPat* __restrict__ pats, const float* __restrict__ seq,
+    const int64_t* __restrict__ off, int n_seq, int64_t L, int D, int64_t nwords, float* __restrict__ dist,
+    unsigned long long* __restrict__ mask) {
+    extern __shared__ float scan_lds[];
+    const int t = threadIdx.x, c = t % kScanTC;
+    const int set = __builtin_amdgcn_readfirstlane(t / kScanTC);
+    const int64_t g0 = (int64_t)blockIdx.x * kScanTC;
+    const ScanPat* grp = pats + (size_t)blockIdx.y * kScanPG;
+    const int ld = D | 1;
+    if (kLds) {
+        const int rows = kScanTC + grp[kScanPG - 1].m - 1;
+        for (int i = t; i < rows * D; i += kScanThreads) {
+            const int r = i / D, d = i - r * D;
+            scan_lds[r * ld + d] = g0 + r < L ? seq[(g0 + r) * D + d] : 0.0f;
+        }
+        __syncthreads();
+    }
+    const ScanPat* mine = grp + set * kScanPT;
+    const float* x[kScanPT];
+    int m[kScanPT];
+    float s[kScanPT];
+#pragma unroll
+    for (int q = 0; q < kScanPT; ++q) {
+        m[q] = mine[q].m;
+        x[q] = pat + mine[q].row0 * D;
+        s[q] = 0.0f;
+    }
+    const int64_t g = g0 + c;
+    const int hm = m[kScanPT - 1];
+    for (int k = 0; k < hm; ++k) {
+        const float* y;
+        if (kLds)
+            y = scan_lds + (c + k) * ld;
+        else
+            y = seq + min(g + k, L - 1) * D;
+        const float* xr[kScanPT];
+        float e[kScanPT];
+#pragma unroll
+        for (int q = 0; q < kScanPT; ++q) {
+            xr[q] = x[q] + (size_t)min(k, m[q] - 1) * D;
+            e[q] = 0.0f;
+        }
+#pragma unroll 4
+        for (int d = 0; d < D; ++d) {
+            const float yv = y[d];
+#pragma unroll
+            for (int q = 0; q < kScanPT; ++q) {
+                const float v = xr[q][d] - yv;
+                e[q] = e[q] + v * v;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kScanPT; ++q)
+            if (k < m[q]) s[q] = s[q] + e[q];
+    }
+    int64_t end = 0;  // of the position's stream
+    if (g < L) end = off[seq_of_row(off, n_seq, g) + 1];
+#pragma unroll
+    for (int q = 0; q < kScanPT; ++q) {
+        const int slot = mine[q].slot;
+        const float dv = sqrtf(s[q]);
+        const bool exists = g < L && g + m[q] <= end;
+        const unsigned long long word = __ballot(exists && dv < mine[q].sigma);
+        if (slot < 0) continue;  // uniform: a group's filler entry
+        if (exists) dist[(size_t)slot * L + g] = dv;
+        if ((t & 63) == 0 && (g >> 6) < nwords) mask[(size_t)slot * nwords + (g >> 6)] = word;
+    }
+}
+
+size_t shapelet_scan_lds_bytes(int m_max, int D) { return sizeof(float) * (size_t)(kScanTC + m_max - 1) * (D | 1); }
+
+void launch_shapelet_scan_dist(const float* pat, const ScanPat* pats, int n_groups, int m_max, bool lds,
+                               const float* seq, const int64_t* off, int n_seq, int64_t L, int D, float* dist,
+                               uint64_t* mask, hipStream_t st) {
+    const dim3 grid((unsigned)((L + kScanTC - 1) / kScanTC), n_groups);
+    const int64_t nwords = (L + 63) / 64;
+    unsigned long long* mk = reinterpret_cast<unsigned long long*>(mask);
+    if (lds) {
+        const size_t shm = shapelet_scan_lds_bytes(m_max, D);
+        static size_t granted = 64 * 1024;
+        if (shm > granted) {
+            OPOSE_HIP_CHECK(hipFuncSetAttribute((const void*)shapelet_scan_dist<true>,
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+            granted = shm;
+        }
+        hipLaunchKernelGGL(shapelet_scan_dist<true>, grid, dim3(kScanThreads), shm, st, pat, pats, seq, off, n_seq, L, D,
+                           nwords, dist, mk);
+    } else {
+        hipLaunchKernelGGL(shapelet_scan_dist<false>, grid, dim3(kScanThreads), 0, st, pat, pats, seq, off, n_seq, L, D,
+                           nwords, dist, mk);
+    }
+}
+
+// the mask of one given distance row (opose_debug_shapelet_pick): bit g = position g exists for a
+// window of m rows and dist[g] < sigma
+__global__ __launch_bounds__(kScanThreads) void shapelet_scan_mask(const float* __restrict__ dist,
+                                                                   const int64_t* __restrict__ off, int n_seq, int64_t L,
+                                                                   int m, float sigma, int64_t nwords,
+                                                                   unsigned long long* __restrict__ mask) {
+    const int64_t g = (int64_t)blockIdx.x * kScanThreads + threadIdx.x;
+    bool hit = false;
+    if (g < L) hit = g + m <= off[seq_of_row(off, n_seq, g) + 1] && dist[g] < sigma;
+    const unsigned long long word = __ballot(hit);
+    if ((threadIdx.x & 63) == 0 && (g >> 6) < nwords) mask[g >> 6] = word;
+}
+
+void launch_shapelet_scan_mask(const float* dist, const int64_t* off, int n_seq, int64_t L, int m, float sigma,
+                               uint64_t* mask, hipStream_t st) {
+    hipLaunchKernelGGL(shapelet_scan_mask, dim3((unsigned)((L + kScanThreads - 1) / kScanThreads)), dim3(kScanThreads), 0,
+                       st, dist, off, n_seq, L, m, sigma, (L + 63) / 64, reinterpret_cast<unsigned long long*>(mask));
+}
+
+// shapelet_scan_pick, one wave per pair (slot, stream j) of the chunk, pair = slot * n_seq + j: the
+// walk over the pair's hits, c ascending, with the state (pre, last entry)
+//   first hit, or 2 * (c - pre) > m:       a new entry (c, dist), pre = c
+//   else dist < the last entry's (strict): the last entry becomes (c, dist), pre = c
+//   else:                                  nothing
+// (the reference's idex - preidx > m / 2 with true division).  The pair's mask words are read 64 a
+// step, one per lane, cut to the pair's positions a .. e - 1 (a word may hold two streams); a
+// ballot names the words with a hit and their set bits are taken in order; dist is read at hits
+// only.  Every lane carries the same state.  write 0: counts[pair] = the entries.  write 1: the
+// entries go to occ_pos / occ_dist from occ_off[pair] on, those at or past cap dropped.
+__global__ __launch_bounds__(64 * kScanPickPairs) void shapelet_scan_pick(
+    const float* __restrict__ dist, const unsigned long long* __restrict__ mask, const int32_t* __restrict__ m_slot,
+    const int64_t* __restrict__ off, int n_seq, int64_t L, int64_t nwords, int n_pairs, int32_t* __restrict__ counts,
+    const int64_t* __restrict__ occ_off, int32_t* __restrict__ occ_pos, float* __restrict__ occ_dist, int64_t cap,
+    int write) {
+    const int lane = threadIdx.x & 63;
+    const int pair = blockIdx.x * kScanPickPairs + (threadIdx.x >> 6);
+    if (pair >= n_pairs) return;  // the whole wave
+    const int slot = pair / n_seq, j = pair - slot * n_seq;
+    const int m = m_slot[slot];
+    const int64_t a = off[j], e = off[j + 1] - m + 1;  // the pair's positions are rows a .. e - 1
+    const int64_t base = write ? occ_off[pair] : 0;
+    int cnt = 0;
+    int64_t pre = 0;
+    float lastd = 0.0f;
+    if (e > a) {
+        const unsigned long long* mw = mask + (size_t)slot * nwords;
+        const float* dr = dist + (size_t)slot * L;
+        const int64_t w0 = a >> 6, w1 = (e - 1) >> 6;
+        for (int64_t wb = w0; wb <= w1; wb += 64) {
+            const int64_t w = wb + lane;
+            unsigned long long bits = 0;
+            if (w <= w1) {
+                bits = mw[w];
+                if (w == w0) bits &= ~0ull << (a & 63);
+                if (w == w1 && (e & 63) != 0) bits &= ~0ull >> (64 - (e & 63));
+            }
+            unsigned long long nz = __ballot(bits != 0);
+            while (nz) {  // uniform
+                const int wi = __builtin_ctzll(nz);
+                nz &= nz - 1;
+                const unsigned lo = (unsigned)__shfl((int)(unsigned)bits, wi);
+                const unsigned hi = (unsigned)__shfl((int)(unsigned)(bits >> 32), wi);
+                unsigned long long wbits = ((unsigned long long)hi << 32) | lo;
+                while (wbits) {
+                    const int64_t g = ((wb + wi) << 6) + __builtin_ctzll(wbits);
+                    wbits &= wbits - 1;
+                    const int64_t c = g - a;
+                    const float d = dr[g];
+                    bool put = false;
+                    if (cnt == 0 || 2 * (c - pre) > m) {
+                        ++cnt;
+                        put = true;
+                    } else if (d < lastd) {
+                        put = true;
+                    }
+                    if (put) {
+                        pre = c;
+                        lastd = d;
+                        const int64_t o = base + cnt - 1;
+                        if (write && lane == 0 && o < cap) {
+                            occ_pos[o] = (int32_t)c;
+                            occ_dist[o] = d;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (!write && lane == 0) counts[pair] = cnt;
+}
+
+void launch_shapelet_scan_pick(const float* dist, const uint64_t* mask, const int32_t* m_slot, const int64_t* off,
+                               int n_seq, int64_t L, int n_pairs, int32_t* counts, const int64_t* occ_off,
+                               int32_t* occ_pos, float* occ_dist, int64_t cap, bool write, hipStream_t st) {
+    hipLaunchKernelGGL(shapelet_scan_pick, dim3((n_pairs + kScanPickPairs - 1) / kScanPickPairs),
+                       dim3(64 * kScanPickPairs), 0, st, dist, reinterpret_cast<const unsigned long long*>(mask), m_slot,
+                       off, n_seq, L, (L + 63) / 64, n_pairs, counts, occ_off, occ_pos, occ_dist, cap, write ? 1 : 0);
+}
+
+// One workgroup: occ_off[i] = *running + the counts before i, for the chunk's n pairs (occ_off
+// points at the chunk's first pair), occ_off[n] = the new running total, which stays on the device
+// for the next chunk.  first: the running total starts at 0.
+__global__ __launch_bounds__(kShpThreads) void shapelet_scan_offsets(const int32_t* __restrict__ counts, int n, int first,
+                                                                     int64_t* __restrict__ running,
+                                                                     int64_t* __restrict__ occ_off) {
+    __shared__ int64_t part[kShpThreads];
+    const int t = threadIdx.x;
+    const int per = (n + kShpThreads - 1) / kShpThreads;
+    const int i0 = min(t * per, n), i1 = min(i0 + per, n);
+    int64_t sum = 0;
+    for (int i = i0; i < i1; ++i) sum += counts[i];
+    part[t] = sum;
+    __syncthreads();
+    if (t == 0) {
+        int64_t run = first ? 0 : *running;
+        for (int i = 0; i < kShpThreads; ++i) {
+            const int64_t v = part[i];
+            part[i] = run;
+            run += v;
+        }
+        *running = run;
+        occ_off[n] = run;
+    }
+    __syncthreads();
+    int64_t acc = part[t];
+    for (int i = i0; i < i1; ++i) {
+        occ_off[i] = acc;
+        acc += counts[i];
+    }
+}
+
+void launch_shapelet_scan_offsets(const int32_t* counts, int n, bool first, int64_t* running, int64_t* occ_off,
+                                  hipStream_t st) {
+    hipLaunchKernelGGL(shapelet_scan_offsets, dim3(1), dim3(kShpThreads), 0, st, counts, n, first ? 1 : 0, running,
+                       occ_off);
 }
 
 }  // namespace opose

@@ -115,6 +115,8 @@ SIGNATURES = {
     "opose_shapelet_mindist_lengths": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _I]),
     "opose_shapelet_find_lengths": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I]),
     "opose_debug_shapelet_score": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "opose_shapelet_scan": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _I]),
+    "opose_debug_shapelet_pick": (_I, [_P, _P, _P, _I, _I, C.c_float, _P, _P, _P, _L]),
 }
 EXPORTED = list(SIGNATURES)
 

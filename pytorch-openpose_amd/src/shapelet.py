@@ -208,6 +208,64 @@ def shapelet_find_lengths(seq, off, labels, m_lens, max_cands=0, every=False, ha
              "losses": losses[starts[l]:starts[l + 1]] if every else None} for l in range(nl)]
 
 
+SCAN_FIRST_CAP = 1 << 20  # shapelet_scan's first guess at the occurrences when cap is None
+
+
+def shapelet_scan(patterns, sigmas, seq, off, cap=None, max_pats=0, handle=None):
+    """Every occurrence of the patterns (a list of [m_p, D] arrays or tensors) in the streams of the
+    ragged batch seq [L, D] / off (opose_shapelet_scan; include/opose.h states the rule): position c
+    of a stream is a hit of pattern p when its distance is below sigmas[p], and each run of
+    neighbouring hits is thinned to one occurrence as the reference's AugmentateOneShapelet does.
+    Returns {"off": int64 [n_pat * n_seq + 1] (pattern-major), "pos": int32 [total], "dist": float32
+    [total]}.  Host in gives host out; a CUDA seq gives CUDA tensors on torch's current stream.
+    cap: room for that many occurrences (more is an OposeError of code OPOSE_E_CAPACITY on the host
+    path; on the device path the entries past cap are missing and off[-1] tells); None: a first
+    guess, and one retry with the exact total when it was too small."""
+    import torch
+    dev = _is_dev(seq)
+    off = np.ascontiguousarray(off, np.int64)
+    sig = np.ascontiguousarray(sigmas, np.float32).reshape(-1)
+    if len(sig) != len(patterns):
+        raise ValueError("one sigma per pattern")
+    pat_off = _offsets([len(p) for p in patterns])
+    if dev:
+        seq = seq.to(torch.float32).contiguous()
+        pat = torch.cat([torch.as_tensor(p, dtype=torch.float32, device=seq.device).reshape(len(p), -1)
+                         for p in patterns], dim=0).contiguous() if len(patterns) else seq[:0]
+    else:
+        seq = np.ascontiguousarray(seq, np.float32)
+        pat = np.ascontiguousarray(np.concatenate([np.asarray(p, np.float32).reshape(len(p), -1) for p in patterns])
+                                   if len(patterns) else seq[:0])
+    D = seq.shape[1]
+    if len(patterns) and pat.shape[1] != D:
+        raise ValueError("patterns and streams differ in their feature columns")
+    n_pat, n_seq = len(patterns), len(off) - 1
+    h = handle or default_handle(seq.device.index if dev else 0)
+    occ_off = _empty(dev, seq, max(n_pat * n_seq, 0) + 1, np.int64)
+
+    def call(room):
+        pos, dist = _empty(dev, seq, max(room, 1), np.int32), _empty(dev, seq, max(room, 1), np.float32)
+        _run(h, dev, lib.opose_shapelet_scan, _native._ptr(pat), pat_off.ctypes.data, n_pat, sig.ctypes.data,
+             _native._ptr(seq), off.ctypes.data, n_seq, D, int(max_pats), _native._ptr(occ_off), _native._ptr(pos),
+             _native._ptr(dist), int(room), _native.DEVICE_IO if dev else 0)
+        return pos, dist
+
+    room = SCAN_FIRST_CAP if cap is None else int(cap)
+    try:
+        pos, dist = call(room)
+    except _native.OposeError as e:
+        if cap is not None or e.code != _native.OPOSE_E_CAPACITY:
+            raise
+        room = int(occ_off[-1])
+        pos, dist = call(room)
+    total = int(occ_off[-1])  # (the device path waits here for the call)
+    if dev and cap is None and total > room:
+        room = total
+        pos, dist = call(room)
+    n = min(total, room)
+    return {"off": occ_off, "pos": pos[:n], "dist": dist[:n]}
+
+
 class ShapeletMatrixModel:
     """The reference's brute-force shapelet model: train() keeps the window of a positive clip whose
     distances to all clips separate the labels best."""
