@@ -696,9 +696,17 @@ int opose_debug_gauss_nms(opose_t* h, const void* maps, int is_f32, int NP, int 
  * channels [coff, coff + P) of the x8 maps mid [N,Cm,Hs,Ws] float32 resized to H x W with source
  * steps 1 / (H / Hs), 1 / (W / Ws), then as above on the N * P float32 maps: cnt [N * P], list /
  * score [N * P,cap].  OPOSE_E_ARG without a launch for a geometry the kernel does not take (an
- * identity resize, or a vertical source step above 34 / 55) */
+ * identity resize, a vertical source step above 34 / 55, or Ws above 4096) */
 int opose_debug_gauss_nms_resize(opose_t* h, const float* mid, int N, int Cm, int coff, int P, int Hs, int Ws, int H,
                                  int W, double thre, int cap, int32_t* cnt, int32_t* list, double* score);
+/* The same call, with what its screen launch decided: hot_tiles [tiles], tiles = N * P *
+ * ceil(H / 30) * ceil(W / 102), holds in its first *hot_cnt entries the ids (np * tile rows + ty) *
+ * tile columns + tx of the tiles whose sources can reach thre (in no defined order; the others -1).
+ * max_grid > 0 caps the NMS launch's grid, so that few workgroups loop over many tiles (0: the
+ * production grid) */
+int opose_debug_gauss_hot_tiles(opose_t* h, const float* mid, int N, int Cm, int coff, int P, int Hs, int Ws, int H,
+                                int W, double thre, int cap, int max_grid, int32_t* cnt, int32_t* list, double* score,
+                                int32_t* hot_cnt, int32_t* hot_tiles);
 /* src/body.py:51-67 / src/hand.py:43-56, the heat average of n scales: channels [coff, coff + C) of
  * mids[s] [N,Cm,Hs[s],Ws[s]] float32, each resized to H x W (copied where it has that size), divided
  * by n in float32 and added in scale order from 0.0 in float64 -> avg [N * C,H,W] float64.

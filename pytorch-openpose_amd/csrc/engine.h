@@ -418,6 +418,8 @@ struct opose_ctx {
     std::vector<std::vector<int>> sched_host;  // sources of the asynchronous uploads
     opose::DevBuf frames, mids[2][opose::kMaxScales], avg, cnt, list, peak_pos, part_cnt, score, conn, conn_cnt, records, maps_in,
         hlab, hsums, hpeaks, hfound, list_score, hsel;
+    // gauss_nms_resize's hot-tile list (its count is the word after the peak counts in `cnt`)
+    opose::DevBuf hot_tiles;
     // fast-mode hand extraction (opose_batch_hand_boxes / _crops / _extract): staged poses, the
     // boxes and per-slot status, staged results
     opose::DevBuf hx_motion, hx_boxes, hx_status, hx_crops, hx_handmat;

@@ -999,10 +999,10 @@ struct DebugPeaks {
     int *cnt, *list;
     double* score;
     DebugPeaks(opose_ctx* h, int NP_, int cap) : NP(NP_), nl((size_t)NP_ * cap) {
-        cnt = cb.ensure<int>((size_t)NP, h->stream);
+        cnt = cb.ensure<int>((size_t)NP + 1, h->stream);  // + gauss_nms_resize's hot-tile count
         list = lb.ensure<int>(nl, h->stream);
         score = sb.ensure<double>(nl, h->stream);
-        OPOSE_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * NP, h->stream));
+        OPOSE_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * ((size_t)NP + 1), h->stream));
         OPOSE_HIP_CHECK(hipMemsetAsync(list, 0xff, sizeof(int) * nl, h->stream));  // unused slots: -1
         OPOSE_HIP_CHECK(hipMemsetAsync(score, 0, sizeof(double) * nl, h->stream));
     }
@@ -1030,8 +1030,11 @@ int opose_debug_gauss_nms(opose_t* h, const void* maps, int is_f32, int NP, int 
     return OPOSE_OK;
 }
 
-int opose_debug_gauss_nms_resize(opose_t* h, const float* mid, int N, int Cm, int coff, int P, int Hs, int Ws, int H,
-                                 int W, double thre, int cap, int32_t* cnt, int32_t* list, double* score) {
+// opose_debug_gauss_nms_resize / opose_debug_gauss_hot_tiles: the production launch pair on the
+// handle's own hot-tile buffer; the hot count is the word after the peak counts, as in peak_ws
+static int debug_gauss_resize(opose_t* h, const float* mid, int N, int Cm, int coff, int P, int Hs, int Ws, int H, int W,
+                              double thre, int cap, int max_grid, int32_t* cnt, int32_t* list, double* score,
+                              int32_t* hot_cnt, int32_t* hot_tiles) {
     if (!h || !mid || !cnt || !list || !score || N <= 0 || P <= 0 || coff < 0 || coff + P > Cm) return OPOSE_E_ARG;
     if (Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0 || cap <= 0 || (int64_t)H * W > 0x7fffffff) return OPOSE_E_ARG;
     const double sy = 1.0 / ((double)H / Hs), sx = 1.0 / ((double)W / Ws);  // as geom_from_pads
@@ -1041,11 +1044,29 @@ int opose_debug_gauss_nms_resize(opose_t* h, const float* mid, int N, int Cm, in
         DevBuf mb;
         const float* md = to_device(h, mb, mid, (size_t)N * Cm * Hs * Ws);
         DebugPeaks out(h, N * P, cap);
+        const size_t nt = (size_t)gauss_nms_resize_tiles(N, P, H, W);
+        int* hot = h->hot_tiles.ensure<int>(nt, h->stream);
+        if (hot_tiles) OPOSE_HIP_CHECK(hipMemsetAsync(hot, 0xff, sizeof(int) * nt, h->stream));  // unused slots: -1
         launch_gauss_nms_resize(md, Cm, coff, P, N, Hs, Ws, H, W, sy, sx, thre, cap, out.cnt, out.list, out.score,
-                                h->stream);
+                                out.cnt + out.NP, hot, max_grid, h->stream);
+        if (hot_cnt) to_host(h, hot_cnt, out.cnt + out.NP, 1);
+        if (hot_tiles) to_host(h, hot_tiles, hot, nt);
         out.fetch(h, cnt, list, score);
     });
     return OPOSE_OK;
+}
+
+int opose_debug_gauss_nms_resize(opose_t* h, const float* mid, int N, int Cm, int coff, int P, int Hs, int Ws, int H,
+                                 int W, double thre, int cap, int32_t* cnt, int32_t* list, double* score) {
+    return debug_gauss_resize(h, mid, N, Cm, coff, P, Hs, Ws, H, W, thre, cap, 0, cnt, list, score, nullptr, nullptr);
+}
+
+int opose_debug_gauss_hot_tiles(opose_t* h, const float* mid, int N, int Cm, int coff, int P, int Hs, int Ws, int H,
+                                int W, double thre, int cap, int max_grid, int32_t* cnt, int32_t* list, double* score,
+                                int32_t* hot_cnt, int32_t* hot_tiles) {
+    if (!hot_cnt || !hot_tiles || max_grid < 0) return OPOSE_E_ARG;
+    return debug_gauss_resize(h, mid, N, Cm, coff, P, Hs, Ws, H, W, thre, cap, max_grid, cnt, list, score, hot_cnt,
+                              hot_tiles);
 }
 
 int opose_debug_heat_scales(opose_t* h, int n, const float* const* mids, const int* Hs, const int* Ws, int N, int Cm,

@@ -96,7 +96,7 @@ struct PeakWS {
 static PeakWS peak_ws(opose_ctx* h, int N) {
     const int cap = h->ppp;
     PeakWS w;
-    w.cnt = h->cnt.ensure<int>((size_t)N * 18, h->stream);
+    w.cnt = h->cnt.ensure<int>((size_t)N * 18 + 1, h->stream);  // + gauss_nms_resize's hot-tile count
     w.list = h->list.ensure<int>((size_t)N * 18 * cap, h->stream);
     w.lscore = h->list_score.ensure<double>((size_t)N * 18 * cap, h->stream);
     w.pos = h->peak_pos.ensure<int>((size_t)N * 18 * cap, h->stream);
@@ -120,7 +120,7 @@ static void peaks_to_records(opose_ctx* h, int N, int H, int W, const PafScales&
     int *cnt = w.cnt, *list = w.list, *pos = w.pos, *pcnt = w.pcnt, *ccnt = w.ccnt;
     double *lscore = w.lscore, *score = w.score;
     Conn* conn = w.conn;
-    OPOSE_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * N * 18, h->stream));
+    OPOSE_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * ((size_t)N * 18 + 1), h->stream));  // and the hot-tile count
     find_peaks(cap, cnt, list, lscore);
     ProfEntry pe;
     h->prof_begin(pe, "peaks_finalize", 0, 0);
@@ -172,7 +172,10 @@ void body_post_reserve(opose_ctx* h, int N, int H, int W, const std::vector<Scal
     for (size_t s = 0; s < gs.size(); ++s)
         h->mid(slot0 + (int)s).ensure<float>(body_mid_heat(N, gs[s]) + (size_t)N * 38 * gs[s].hl * gs[s].wl, h->stream);
     peak_ws(h, N);
-    if (!body_post_resizes_in_nms(H, W, gs)) h->avg.ensure<double>((size_t)N * 18 * H * W, h->stream);
+    if (body_post_resizes_in_nms(H, W, gs))
+        h->hot_tiles.ensure<int>((size_t)gauss_nms_resize_tiles(N, 18, H, W), h->stream);
+    else
+        h->avg.ensure<double>((size_t)N * 18 * H * W, h->stream);
 }
 
 // post-network body path from per-scale mid sets (body_to_mid; scale s in set slot0 + s) to records
@@ -190,14 +193,16 @@ void body_post_common(opose_ctx* h, int N, int H, int W, const std::vector<Scale
         if (body_post_resizes_in_nms(H, W, gs)) {
             // one scale, a true upsampling resize (the reference's 368-row frames at scale 0.5): the
             // resize runs inside the NMS tiles (post.hip gauss_nms_resize) and tiles whose sources
-            // cannot produce a peak are dropped, so no full-resolution map is written or read.
+            // cannot produce a peak are dropped by a screen launch before it (both booked as
+            // gauss_nms_resize), so no full-resolution map is written or read.
             // float64-VALU bound: flops = the reference filter's 2 x 37 float64 operations per
             // full-resolution part-map pixel (bench.py GAUSS_OPS_PER_PIXEL); bytes: the x8 heat
             // channels the tiles read
             h->prof_begin(pe, "gauss_nms_resize", 74.0 * N * 18 * (double)H * W,
                           (double)N * 18 * 4.0 * gs[0].Hs * gs[0].Ws);
+            int* hot = h->hot_tiles.ensure<int>((size_t)gauss_nms_resize_tiles(N, 18, H, W), h->stream);
             launch_gauss_nms_resize(S.mid[0], 18, 0, 18, N, gs[0].Hs, gs[0].Ws, H, W, gs[0].up_sy, gs[0].up_sx,
-                                    p.thre1, cap, cnt, list, lscore, h->stream);
+                                    p.thre1, cap, cnt, list, lscore, cnt + (size_t)N * 18, hot, 0, h->stream);
             h->prof_end(pe);
             return;
         }

@@ -223,11 +223,16 @@ void launch_shapelet_scan_offsets(const int32_t* counts, int n, bool first, int6
 void launch_gauss_nms(const void* avg, bool f32, int NP, int H, int W, double thre, int cap, int* cnt, int* list,
                       double* list_score, hipStream_t st);
 // single scale: heat_full's resize of mid channels [coff, coff+P) fused into the wide NMS
-// (requires gauss_nms_resize_fits: a true resize with source step sy <= 0.618)
+// (requires gauss_nms_resize_fits: a true resize with source step sy <= 0.618 from a map of at
+// most 4096 columns).  Two launches: a screen that lists the tiles whose sources can reach the
+// threshold (hot_list: gauss_nms_resize_tiles ints, ids (np * tile rows + ty) * tile columns + tx
+// in no defined order; *hot_cnt: their number, zero on entry), then the NMS over that list in a
+// fixed grid (max_grid > 0 caps it: the debug hook's way to make few workgroups loop).
 bool gauss_nms_resize_fits(int Hs, int Ws, int H, int W, double sy);
+int gauss_nms_resize_tiles(int N, int P, int H, int W);
 void launch_gauss_nms_resize(const float* mid, int Cm, int coff, int P, int N, int Hs, int Ws, int H, int W, double sy,
-                             double sx, double thre, int cap, int* cnt, int* list, double* list_score,
-                             hipStream_t st);
+                             double sx, double thre, int cap, int* cnt, int* list, double* list_score, int* hot_cnt,
+                             int* hot_list, int max_grid, hipStream_t st);
 // Batch_body fast mode: 5x5 Gaussian (reflect pad, srcmx/utilmx.py:246-263) + findpeaks_torch
 // (srcmx/utilmx.py:230-243) on heat [NP][H][W] float; scores = blurred values
 void launch_blur5_nms(const float* heat, int NP, int H, int W, double thre, int cap, int* cnt, int* list,

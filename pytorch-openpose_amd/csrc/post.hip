@@ -1,3 +1,4 @@
+#include <algorithm>
 #include <cstdlib>
 #include <stdexcept>
 // post.hip — the post-network Body path as wavefront-parallel kernels.
@@ -212,17 +213,15 @@ __device__ __forceinline__ void gauss_wide_load(const T* __restrict__ m, int H, 
 // smoothing + NMS of one wide tile from the vertical pass's register window (every thread of
 // the workgroup calls it; sv may alias a staging buffer the window was built from: the first
 // barrier below comes after every window is complete).  score_at(y, x) = map_ori[y, x].
+// hot: whether any entry of this thread's window reaches gauss_skip_below(thre) (the caller tests
+// the values in the type it holds them in); the tile is dropped when no thread's does.
 template <typename ScoreAt>
-__device__ __forceinline__ void gauss_wide_tail(double (&win)[WVH + 24], double (*sv)[WVW + 1], int H, int W, int x0,
-                                                int y0, int np, double thre, int cap, int* __restrict__ cnt,
+__device__ __forceinline__ void gauss_wide_tail(double (&win)[WVH + 24], bool hot, double (*sv)[WVW + 1], int H, int W,
+                                                int x0, int y0, int np, double thre, int cap, int* __restrict__ cnt,
                                                 int* __restrict__ list, double* __restrict__ list_score,
                                                 ScoreAt score_at) {
     const int tid = threadIdx.x;
     const int c = tid & (WVW - 1), h = tid >> 7;
-    bool hot = false;
-    const double skip_below = gauss_skip_below(thre);
-#pragma unroll
-    for (int i = 0; i < WVH + 24; ++i) hot |= win[i] >= skip_below;
     if (!__syncthreads_or(hot)) return;  // no smoothed value can pass `> thre` (see gauss_tile)
 #pragma unroll
     for (int i = 0; i < WVH; ++i) sv[h * WVH + i][c] = gauss25(win, i);
@@ -240,11 +239,24 @@ __device__ __forceinline__ void gauss_wide_tail(double (&win)[WVH + 24], double 
     for (int e = tid; e < WTW * WTH; e += 256) {
         const int r = e / WTW, cc = e - r * WTW;
         const int y = y0 + r, x = x0 + cc;
-        if (y >= H || x >= W) continue;
+        // `> thre` first: few pixels pass it, and a wave none of whose pixels does skips the four
+        // neighbour reads (a NaN fails either test)
+        const bool above = y < H && x < W && sv[r + 1][cc + 1] > thre;
+        if (!__ballot(above)) continue;
+        if (!above) continue;
         const double v = sv[r + 1][cc + 1];
-        if (nms4(sv, r, cc, y, x, H, W, v) && v > thre)
+        if (nms4(sv, r, cc, y, x, H, W, v))
             push_peak(cnt, list, list_score, np, cap, y * W + x, [&] { return score_at(y, x); });
     }
+}
+
+// whether any entry of a vertical-pass window reaches gauss_skip_below(thre)
+__device__ __forceinline__ bool gauss_window_hot(const double (&win)[WVH + 24], double thre) {
+    bool hot = false;
+    const double skip_below = gauss_skip_below(thre);
+#pragma unroll
+    for (int i = 0; i < WVH + 24; ++i) hot |= win[i] >= skip_below;
+    return hot;
 }
 
 template <typename T>
@@ -264,7 +276,7 @@ __global__ __launch_bounds__(256) void gauss_nms_wide(const T* __restrict__ avg,
         gauss_wide_load<T, 1>(m, H, W, x0, y0, c, h, win);
     else
         gauss_wide_load<T, 2>(m, H, W, x0, y0, c, h, win);
-    gauss_wide_tail(win, sv, H, W, x0, y0, np, thre, cap, cnt, list, list_score,
+    gauss_wide_tail(win, gauss_window_hot(win, thre), sv, H, W, x0, y0, np, thre, cap, cnt, list, list_score,
                     [&](int y, int x) { return (double)m[(size_t)y * W + x]; });
 }
 
@@ -277,94 +289,244 @@ __global__ __launch_bounds__(256) void gauss_nms_wide(const T* __restrict__ avg,
 // combines its 40 window rows from them -- cubic_resize_rows<1>'s arithmetic in its order, so the
 // window holds exactly the values launch_heat_full_f32 would have stored (0.f + v).  The score of
 // a peak (map_ori[y, x]) is resampled from mid with cubic_sample_f32 (bit-identical, rare).
+//
+// Two launches.  gauss_resize_screen decides which tiles are cold and writes the others' ids as a
+// compact list; gauss_nms_resize is a fixed grid whose workgroups stride over that list, so a cold
+// tile costs its share of the screen and no workgroup of its own.
+//
+// The cold criterion, decided on the source before any arithmetic: every resized value of a
+// tile's footprint is sum_i ty.c[i] * sum_j tx.c[j] * q_ij over the source values q at the tap
+// rows lo .. hi and tap columns of the footprint, and the cubic (A = -0.75) weights of one axis
+// sum to at most 1.375 in absolute value (t = 0.5), so |resized| <= 1.890625 * max|q| (float32
+// rounding: < 1e-6 relative; 1.9 covers it).  The smoothing is a convex combination of the resized
+// footprint, so when 1.9 * max|q| is below the threshold no output of the tile can pass `> thre`:
+// nothing to resize, filter or report (the exact criterion gauss_wide_tail applies to the resized
+// values, taken earlier and more conservatively).  NaN sources count as below, as in
+// gauss_wide_tail (a NaN only ever removes peaks).
 constexpr int GR_FOOT = WVR + 24;  // 56 footprint rows
 constexpr int GR_MAXR = 40;        // staged source rows: 55 * sy + 6 <= 40
 static_assert(GR_MAXR * WVW * 4 <= WVR * (WVW + 1) * 8, "staged rows fit in the smoothing plane");
+constexpr int GS_THREADS = 1024;   // screen: one workgroup per map
+constexpr int GS_ROWS = GS_THREADS / 256;  // row groups of its column pass
+constexpr int GS_MAXW = 4096;      // source columns whose maxima it holds (gauss_nms_resize_fits)
+constexpr int GS_PEND = 1024;      // hot tile ids held back for one append
+constexpr int GS_CHUNK = 512;      // tiles of a tile row decided between two looks at the fill
 
+// the tile id of the hot list: tile (tx, ty) of map np, decoded as tile_coords decodes a workgroup
+__host__ __device__ __forceinline__ int gauss_tile_id(int ntx, int nty, int tx, int ty, int np) {
+    return (np * nty + ty) * ntx + tx;
+}
+
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
+    return v;
+}
+
+// The screen: one workgroup per map reads the map's source plane about twice (consecutive tile
+// rows share tap rows) instead of each tile reading its 2.3x-overlapping footprint with four taps
+// per footprint column.  Per tile row: the maximum of |q| over the tap rows lo .. hi of every
+// source column (LDS, as the bit pattern of a non-negative float, which orders like the float;
+// fmaxf skips a NaN), then per tile the maximum over the tap columns of its 128 footprint columns
+// -- the values gauss_nms_resize's staging loop reads, no more and no fewer.  Hot tile ids gather
+// in LDS and are appended with one atomic on *hot_cnt per map (per GS_PEND tiles of a huge one):
+// the list's order is not defined.  *hot_cnt is zero on entry (the caller's clear).
+__global__ __launch_bounds__(GS_THREADS) void gauss_resize_screen(const float* __restrict__ mid, int Cm, int coff,
+                                                                  int P, int Hs, int Ws, int H, int W, double sy,
+                                                                  double sx, double thre, int* __restrict__ hot_cnt,
+                                                                  int* __restrict__ hot_list) {
+    __shared__ unsigned s_col[GS_MAXW];
+    __shared__ int s_pend[GS_PEND];
+    __shared__ int s_lo, s_hi, s_npend, s_base;
+    const int np = blockIdx.x;
+    const int n = np / P, p = np - n * P;
+    const float* plane = mid + ((size_t)n * Cm + coff + p) * Hs * Ws;
+    const int ntx = (W + WTW - 1) / WTW, nty = (H + WTH - 1) / WTH;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double skip_below = gauss_skip_below(thre);
+    if (tid == 0) s_npend = 0;
+    // append the held-back ids (every thread calls it, after a barrier that follows the last push)
+    auto flush = [&]() {
+        const int npend = s_npend;
+        if (tid == 0) s_base = atomicAdd(hot_cnt, npend);
+        __syncthreads();
+        const int base = s_base;
+        for (int i = tid; i < npend; i += GS_THREADS) hot_list[base + i] = s_pend[i];
+        __syncthreads();
+        if (tid == 0) s_npend = 0;
+        __syncthreads();
+    };
+    for (int ty = 0; ty < nty; ++ty) {
+        const int y0 = ty * WTH;
+        if (wave == 0) {  // tap rows of the 56 footprint rows (reflected like scipy)
+            int l = 0x7fffffff, u = -1;
+            if (lane < GR_FOOT) {
+                const CubicTap t = cubic_tap(reflect_idx(y0 - 13 + lane, H), sy, Hs);
+                l = t.i[0];
+                u = t.i[3];
+            }
+            l = wave_min(l);
+            u = wave_max(u);
+            if (lane == 0) {
+                s_lo = l;
+                s_hi = u;
+            }
+        }
+        for (int j = tid; j < Ws; j += GS_THREADS) s_col[j] = 0u;
+        __syncthreads();
+        const int lo = s_lo, hi = s_hi;
+        int held = s_npend;  // read where no wave pushes: every thread takes the same branch on it
+        {
+            const int g = tid >> 8;  // row group: rows lo + g, lo + g + GS_ROWS, ..
+            for (int j = tid & 255; j < Ws; j += 256) {
+                const float* q = plane + (size_t)(lo + g) * Ws + j;
+                float mx = 0.f;
+#pragma unroll 4
+                for (int r = lo + g; r <= hi; r += GS_ROWS, q += (size_t)GS_ROWS * Ws) mx = fmaxf(mx, fabsf(*q));
+                atomicMax(&s_col[j], __float_as_uint(mx));
+            }
+        }
+        __syncthreads();
+        for (int tx0 = 0; tx0 < ntx; tx0 += GS_CHUNK) {
+            if (held > GS_PEND - GS_CHUNK) {
+                flush();
+                held = 0;
+            }
+            const int tx1 = min(ntx, tx0 + GS_CHUNK);
+            for (int tx = tx0 + wave; tx < tx1; tx += GS_THREADS / 64) {  // a wave per tile
+                const int x0 = tx * WTW;
+                unsigned m = 0u;
+#pragma unroll
+                for (int k = 0; k < WVW / 64; ++k) {
+                    const CubicTap t = cubic_tap(reflect_idx(x0 - 13 + lane + 64 * k, W), sx, Ws);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) m = max(m, s_col[t.i[i]]);
+                }
+                m = (unsigned)wave_max((int)m);  // bit patterns of non-negative floats: below 2^31
+                if (lane == 0 && 1.9 * (double)__uint_as_float(m) >= skip_below)
+                    s_pend[atomicAdd(&s_npend, 1)] = gauss_tile_id(ntx, nty, tx, ty, np);
+            }
+            __syncthreads();
+            if (tx1 < ntx) {  // a tile row of more than GS_CHUNK tiles
+                held = s_npend;
+                __syncthreads();
+            }
+        }
+    }
+    if (s_npend > 0) flush();
+}
+
+// smallest float32 f with (double)f >= x, so that `v >= f` in float32 decides `(double)v >= x`
+__device__ __forceinline__ float float_not_below(double x) {
+    float f = (float)x;
+    if ((double)f < x) f = nextafterf(f, __builtin_inff());
+    return f;
+}
+
+// grid: any; workgroup b takes entries b, b + gridDim.x, .. of the hot list (through the
+// XCD-contiguous order, guide T1: a map's hot tiles lie together in the list and re-read each
+// other's halos, so they share an L2).  No workgroup waits for another.
 __global__ __launch_bounds__(256) void gauss_nms_resize(const float* __restrict__ mid, int Cm, int coff, int P, int Hs,
                                                         int Ws, int H, int W, double sy, double sx, double thre,
                                                         int cap, int* __restrict__ cnt, int* __restrict__ list,
-                                                        double* __restrict__ list_score) {
+                                                        double* __restrict__ list_score,
+                                                        const int* __restrict__ hot_cnt,
+                                                        const int* __restrict__ hot_list) {
     __shared__ double sv[WVR][WVW + 1];
     __shared__ CubicTap s_ty[GR_FOOT];
     __shared__ int s_lo, s_hi;
     float (*hs)[WVW] = reinterpret_cast<float (*)[WVW]>(&sv[0][0]);
-    int x0, y0, np;
-    tile_coords<WTW, WTH>(H, W, x0, y0, np);
-    const int n = np / P, p = np - n * P;
-    const float* plane = mid + ((size_t)n * Cm + coff + p) * Hs * Ws;
+    const int ntx = (W + WTW - 1) / WTW, nty = (H + WTH - 1) / WTH;
     const int tid = threadIdx.x;
     const int c = tid & (WVW - 1), h = tid >> 7;
-    if (tid == 0) {
-        s_lo = 0x7fffffff;
-        s_hi = -1;
-    }
-    __syncthreads();
-    if (tid < GR_FOOT) {  // vertical taps of the footprint rows (reflected like scipy)
-        const CubicTap ty = cubic_tap(reflect_idx(y0 - 13 + tid, H), sy, Hs);
-        s_ty[tid] = ty;
-        atomicMin(&s_lo, ty.i[0]);
-        atomicMax(&s_hi, ty.i[3]);
-    }
-    __syncthreads();
-    const int lo = s_lo, hi = s_hi;
-    {
-        const CubicTap tx = cubic_tap(reflect_idx(x0 - 13 + c, W), sx, Ws);
-        // Cold-tile skip, decided on the source before any arithmetic: every resized value of the
-        // footprint is sum_i ty.c[i] * sum_j tx.c[j] * q_ij over the source values q this loop
-        // reads, and the cubic (A = -0.75) weights of one axis sum to at most 1.375 in absolute
-        // value (t = 0.5), so |resized| <= 1.890625 * max|q| (float32 rounding: < 1e-6 relative;
-        // 1.9 covers it).  The smoothing is a convex combination of the resized footprint, so
-        // when 1.9 * max|q| is below the threshold no output of the tile can pass `> thre`:
-        // nothing to resize, filter or report (the exact criterion gauss_wide_tail applies to
-        // the resized values, taken earlier and more conservatively).  NaN sources count as
-        // below, as in gauss_wide_tail (a NaN only ever removes peaks).
-        // One pass over the source: the horizontal resize of every footprint row goes to LDS
-        // while the same loads feed the bound (a cold tile then returns without a second read
-        // of its sources; a hot one has its rows staged already)
-        float mx = 0.f;
-        for (int r0 = lo + h; r0 <= hi; r0 += 16) {  // 8 rows per round, loads issued first
-            float q[8][4];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const float* row = plane + (size_t)min(r0 + 2 * k, hi) * Ws;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) q[k][j] = row[tx.i[j]];
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mx = fmaxf(mx, fabsf(q[k][j]));
-                const float v = cubic_dot4(q[k][0], q[k][1], q[k][2], q[k][3], tx.c);
-                if (r0 + 2 * k <= hi) hs[r0 + 2 * k - lo][c] = v;
-            }
+    const float hot_from = float_not_below(gauss_skip_below(thre));
+    const int count = *hot_cnt;
+    for (int e = blockIdx.x; e < count; e += gridDim.x) {
+        const int id = hot_list[xcd_contiguous_id(count, e)];
+        const int x0 = (id % ntx) * WTW, y0 = (id / ntx % nty) * WTH, np = id / ntx / nty;
+        const int n = np / P, p = np - n * P;
+        const float* plane = mid + ((size_t)n * Cm + coff + p) * Hs * Ws;
+        if (tid == 0) {
+            s_lo = 0x7fffffff;
+            s_hi = -1;
         }
-        // (the vote is also the barrier before the vertical pass reads hs)
-        if (!__syncthreads_or(1.9 * (double)mx >= gauss_skip_below(thre))) return;
-    }
-    double win[WVH + 24];
+        __syncthreads();
+        if (tid < GR_FOOT) {  // vertical taps of the footprint rows (reflected like scipy)
+            const CubicTap ty = cubic_tap(reflect_idx(y0 - 13 + tid, H), sy, Hs);
+            s_ty[tid] = ty;
+            atomicMin(&s_lo, ty.i[0]);
+            atomicMax(&s_hi, ty.i[3]);
+        }
+        __syncthreads();
+        const int lo = s_lo, hi = s_hi;
+        {
+            // the horizontal resize of every footprint row, once, into LDS
+            const CubicTap tx = cubic_tap(reflect_idx(x0 - 13 + c, W), sx, Ws);
+            for (int r0 = lo + h; r0 <= hi; r0 += 16) {  // 8 rows per round, loads issued first
+                float q[8][4];
 #pragma unroll
-    for (int i = 0; i < WVH + 24; ++i) {
-        const CubicTap ty = s_ty[h * WVH + i];
-        const float o =
-            cubic_dot4(hs[ty.i[0] - lo][c], hs[ty.i[1] - lo][c], hs[ty.i[2] - lo][c], hs[ty.i[3] - lo][c], ty.c);
-        win[i] = (double)(0.f + o);
+                for (int k = 0; k < 8; ++k) {
+                    const float* row = plane + (size_t)min(r0 + 2 * k, hi) * Ws;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) q[k][j] = row[tx.i[j]];
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const float v = cubic_dot4(q[k][0], q[k][1], q[k][2], q[k][3], tx.c);
+                    if (r0 + 2 * k <= hi) hs[r0 + 2 * k - lo][c] = v;
+                }
+            }
+            __syncthreads();
+        }
+        // the exact test (gauss_window_hot) on the float32 values, before they widen
+        double win[WVH + 24];
+        bool hot = false;
+#pragma unroll
+        for (int i = 0; i < WVH + 24; ++i) {
+            const CubicTap ty = s_ty[h * WVH + i];
+            const float o = 0.f + cubic_dot4(hs[ty.i[0] - lo][c], hs[ty.i[1] - lo][c], hs[ty.i[2] - lo][c],
+                                             hs[ty.i[3] - lo][c], ty.c);
+            hot |= o >= hot_from;
+            win[i] = (double)o;
+        }
+        gauss_wide_tail(win, hot, sv, H, W, x0, y0, np, thre, cap, cnt, list, list_score, [&](int y, int x) {
+            return (double)(0.f + cubic_sample_f32(plane, Ws, cubic_tap(y, sy, Hs), cubic_tap(x, sx, Ws)));
+        });
+        __syncthreads();  // the next tile's taps and staged rows overwrite s_ty and sv
     }
-    gauss_wide_tail(win, sv, H, W, x0, y0, np, thre, cap, cnt, list, list_score, [&](int y, int x) {
-        return (double)(0.f + cubic_sample_f32(plane, Ws, cubic_tap(y, sy, Hs), cubic_tap(x, sx, Ws)));
-    });
 }
 
 bool gauss_nms_resize_fits(int Hs, int Ws, int H, int W, double sy) {
-    return !(Hs == H && Ws == W) && 55.0 * sy + 6.0 <= (double)GR_MAXR;
+    return !(Hs == H && Ws == W) && 55.0 * sy + 6.0 <= (double)GR_MAXR && Ws <= GS_MAXW;
 }
 
+int gauss_nms_resize_tiles(int N, int P, int H, int W) { return tile_count<WTW, WTH>(H, W, N * P); }
+
+// workgroups per CU of gauss_nms_resize's fixed grid (its 33 KB of LDS allow four)
+constexpr int GR_WG_PER_CU = 4;
+
 void launch_gauss_nms_resize(const float* mid, int Cm, int coff, int P, int N, int Hs, int Ws, int H, int W, double sy,
-                             double sx, double thre, int cap, int* cnt, int* list, double* list_score,
-                             hipStream_t st) {
+                             double sx, double thre, int cap, int* cnt, int* list, double* list_score, int* hot_cnt,
+                             int* hot_list, int max_grid, hipStream_t st) {
     if (!gauss_nms_resize_fits(Hs, Ws, H, W, sy)) throw std::invalid_argument("gauss_nms_resize: scale out of range");
-    hipLaunchKernelGGL(gauss_nms_resize, dim3(tile_count<WTW, WTH>(H, W, N * P)), dim3(256), 0, st, mid, Cm, coff, P,
-                       Hs, Ws, H, W, sy, sx, thre, cap, cnt, list, list_score);
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            throw std::runtime_error("gauss_nms_resize: no compute unit count");
+        return n;
+    }();
+    int grid = std::min(gauss_nms_resize_tiles(N, P, H, W), GR_WG_PER_CU * cus);
+    if (max_grid > 0) grid = std::min(grid, max_grid);
+    hipLaunchKernelGGL(gauss_resize_screen, dim3(N * P), dim3(GS_THREADS), 0, st, mid, Cm, coff, P, Hs, Ws, H, W, sy, sx,
+                       thre, hot_cnt, hot_list);
+    hipLaunchKernelGGL(gauss_nms_resize, dim3(grid), dim3(256), 0, st, mid, Cm, coff, P, Hs, Ws, H, W, sy, sx, thre, cap,
+                       cnt, list, list_score, hot_cnt, hot_list);
 }
 
 // Hand: binary = gaussian_filter(map) > thre (src/hand.py:62-63) as union-find seeds, labelled

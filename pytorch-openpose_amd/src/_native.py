@@ -102,6 +102,7 @@ SIGNATURES = {
     "opose_debug_assemble": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "opose_debug_gauss_nms": (_I, [_P, _P, _I, _I, _I, _I, _D, _I, _P, _P, _P]),
     "opose_debug_gauss_nms_resize": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _D, _I, _P, _P, _P]),
+    "opose_debug_gauss_hot_tiles": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _D, _I, _I, _P, _P, _P, _P, _P]),
     "opose_debug_heat_scales": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "opose_debug_hand_crops": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _I, _P, _P, _P]),
     "opose_debug_hand_backmap": (_I, [_P, _P, _P, _P, _I, _I, _P]),
