@@ -79,16 +79,8 @@ static const T* shp_upload(opose_ctx* h, DevBuf& buf, const std::vector<T>& v) {
     return d;
 }
 
-static void run_mindist(opose_ctx* h, const float* seq, const int64_t* off, int n_seq, int D, int m,
-                        const ShpBlock* blocks, int nb, int nc, int64_t L, float* min2, int32_t* loc) {
-    ProfEntry pe;
-    h->prof_begin(pe, "shapelet_mindist", 3.0 * nc * (double)(L - (int64_t)n_seq * (m - 1)) * D, 8.0 * nc * n_seq);
-    launch_shapelet_mindist(seq, off, n_seq, D, m, blocks, nb, min2, loc, h->stream);
-    h->prof_end(pe);
-}
-
-// The window lengths of a several-lengths call: 1 .. kShpMaxLens of them, each at least 1, strictly
-// ascending.  (shp_check on the last length holds the rest: its limit, and every sequence that long.)
+// The window lengths of a call: 1 .. kShpMaxLens of them, each at least 1, strictly ascending.
+// (shp_check on the last length holds the rest: its limit, and every sequence that long.)
 static int shp_lens_check(opose_ctx* h, const int32_t* m_lens, int n_lens, ShpLens* lens) {
     if (n_lens < 1) {
         h->err = "shapelet: at least one window length";
@@ -116,14 +108,14 @@ static int shp_valid_at(const int64_t* off, const ShpBlock& b, int m) {
     return (int)std::min<int64_t>(std::max<int64_t>(P - b.r0, 0), b.nvalid);
 }
 
-static void run_mindist_lengths(opose_ctx* h, const float* seq, const int64_t* off, int n_seq, int D,
-                                const ShpLens& lens, const ShpBlock* blocks, const ShpLenRows* rows, int nb, int nc,
-                                int64_t L, float* min2, int32_t* loc) {
+static void run_mindist(opose_ctx* h, const float* seq, const int64_t* off, int n_seq, int D, const ShpLens& lens,
+                        const ShpBlock* blocks, const ShpLenRows* rows, int nb, int nc, int64_t L, float* min2,
+                        int32_t* loc) {
     ProfEntry pe;
     const int mx = lens.m[lens.n - 1];
-    h->prof_begin(pe, "shapelet_mindist_lengths", 3.0 * nc * (double)(L - (int64_t)n_seq * (mx - 1)) * D,
+    h->prof_begin(pe, "shapelet_mindist", 3.0 * nc * (double)(L - (int64_t)n_seq * (mx - 1)) * D,
                   8.0 * nc * n_seq * lens.n);
-    launch_shapelet_mindist_lengths(seq, off, n_seq, D, lens, blocks, rows, nb, min2, loc, h->stream);
+    launch_shapelet_mindist(seq, off, n_seq, D, lens, blocks, rows, nb, min2, loc, h->stream);
     h->prof_end(pe);
 }
 
@@ -165,9 +157,33 @@ static int shp_labels_check(opose_ctx* h, const uint8_t* labels, int n_labels, i
     return OPOSE_OK;
 }
 
-// the winner block the select kernel writes when the outputs are host memory:
-// int32 best[4] | double best_loss | float dis[n_seq] | int32 locs[n_seq]
-static size_t shp_best_bytes(int n_seq) { return 24 + 8 * (size_t)n_seq; }
+// Where shapelet_select keeps the winners of nl window lengths over ns sequences.  With host outputs
+// that is one workspace block,
+//   int32 best[nl][4] | double best_loss[nl] | float dis[nl][ns] | int32 locs[nl][ns]
+// (best_loss on a multiple of 8 bytes); with device outputs, the caller's four arrays.
+struct ShpWinners {
+    size_t nl, ns;
+    int32_t* best;
+    double* loss;
+    float* dis;
+    int32_t* locs;
+    static size_t bytes(size_t nl, size_t ns) { return nl * (24 + 8 * ns); }
+    static ShpWinners in_block(uint8_t* block, size_t nl, size_t ns) {
+        return ShpWinners{nl,
+                          ns,
+                          reinterpret_cast<int32_t*>(block),
+                          reinterpret_cast<double*>(block + 16 * nl),
+                          reinterpret_cast<float*>(block + 24 * nl),
+                          reinterpret_cast<int32_t*>(block + (24 + 4 * ns) * nl)};
+    }
+    // queued on the stream; the caller synchronises
+    void to_host(opose_ctx* h, int32_t* hbest, double* hloss, float* hdis, int32_t* hlocs) const {
+        OPOSE_HIP_CHECK(hipMemcpyAsync(hbest, best, 16 * nl, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(hloss, loss, 8 * nl, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(hdis, dis, 4 * nl * ns, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(hlocs, locs, 4 * nl * ns, hipMemcpyDeviceToHost, h->stream));
+    }
+};
 
 }  // namespace opose
 
@@ -230,36 +246,12 @@ int opose_sliding_distance(opose_t* h, const float* pattern, int m, const float*
     return OPOSE_OK;
 }
 
+// One window length is a list of one: the checks, in their order, and the outputs are those of the
+// several-lengths calls below.
 int opose_shapelet_mindist(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int m,
                            const int32_t* cand_seqs, int n_cand_seqs, float* min2, int32_t* loc, int flags) {
-    if (!h || !seq || !off || !cand_seqs || !min2 || !loc || n_cand_seqs < 1) return OPOSE_E_ARG;
-    if (const int rc = shp_check(h, off, n_seq, D, m)) return rc;
-    for (int i = 0; i < n_cand_seqs; ++i)
-        if (cand_seqs[i] < 0 || cand_seqs[i] >= n_seq) return OPOSE_E_ARG;
-    OPOSE_TRY(h, {
-        enter_main(h);
-        const bool od = flags & OPOSE_OUT_DEVICE;
-        const int64_t L = off[n_seq];
-        std::vector<ShpBlock> blocks;
-        std::vector<ShpChunk> chunks;
-        const std::vector<int> cands(cand_seqs, cand_seqs + n_cand_seqs);
-        const int64_t nc = shp_table(off, m, cands, INT32_MAX, blocks, chunks);
-        if (nc > INT32_MAX) throw std::invalid_argument("shapelet: too many candidates for one call");
-        const size_t n_out = (size_t)nc * n_seq;
-        const float* sd = shp_stage(h, h->shp_seq, seq, (size_t)L * D, flags & OPOSE_IN_DEVICE);
-        const int64_t* offd = shp_stage(h, h->shp_off, off, (size_t)n_seq + 1, false);
-        float* md = od ? min2 : h->shp_min2.ensure<float>(n_out, h->stream);
-        int32_t* ld = od ? loc : h->shp_loc.ensure<int32_t>(n_out, h->stream);
-        const ShpBlock* bd = shp_upload(h, h->shp_blocks, blocks);
-        run_mindist(h, sd, offd, n_seq, D, m, bd, (int)blocks.size(), (int)nc, L, md, ld);
-        if (!od) {
-            OPOSE_HIP_CHECK(hipMemcpyAsync(min2, md, n_out * 4, hipMemcpyDeviceToHost, h->stream));
-            OPOSE_HIP_CHECK(hipMemcpyAsync(loc, ld, n_out * 4, hipMemcpyDeviceToHost, h->stream));
-            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
-        }
-        h->prof_drain();
-    });
-    return OPOSE_OK;
+    const int32_t one = m;
+    return opose_shapelet_mindist_lengths(h, seq, off, n_seq, D, &one, 1, cand_seqs, n_cand_seqs, min2, loc, flags);
 }
 
 int opose_debug_shapelet_score(opose_t* h, const float* min2, int n_cand, int n_seq, const uint8_t* labels,
@@ -276,7 +268,7 @@ int opose_debug_shapelet_score(opose_t* h, const float* min2, int n_cand, int n_
         uint8_t* yd = yb.ensure<uint8_t>((size_t)n_labels, h->stream);
         int32_t* nd = nb.ensure<int32_t>((size_t)n_cand, h->stream);
         double* sd = sb.ensure<double>((size_t)n_cand, h->stream);
-        uint8_t* best = bb.ensure<uint8_t>(shp_best_bytes(n_seq), h->stream);
+        const ShpWinners w = ShpWinners::in_block(bb.ensure<uint8_t>(ShpWinners::bytes(1, n_seq), h->stream), 1, n_seq);
         OPOSE_HIP_CHECK(hipMemcpyAsync(md, min2, n * 4, hipMemcpyHostToDevice, h->stream));
         OPOSE_HIP_CHECK(hipMemsetAsync(ld, 0, n * 4, h->stream));
         OPOSE_HIP_CHECK(hipMemcpyAsync(yd, labels, (size_t)n_labels, hipMemcpyHostToDevice, h->stream));
@@ -284,13 +276,11 @@ int opose_debug_shapelet_score(opose_t* h, const float* min2, int n_cand, int n_
         const std::vector<ShpBlock> one{ShpBlock{0, 0, n_cand, 0}};
         const ShpBlock* bd = shp_upload(h, tb, one);
         run_score(h, md, n_cand, n_seq, n_labels, yd, negs, nd, sd);
-        run_select(h, nd, sd, n_cand, bd, 1, md, ld, n_seq, 1, reinterpret_cast<int32_t*>(best),
-                   reinterpret_cast<double*>(best + 16), reinterpret_cast<float*>(best + 24),
-                   reinterpret_cast<int32_t*>(best + 24 + 4 * (size_t)n_seq));
+        run_select(h, nd, sd, n_cand, bd, 1, md, ld, n_seq, 1, w.best, w.loss, w.dis, w.locs);
         OPOSE_HIP_CHECK(hipMemcpyAsync(num, nd, (size_t)n_cand * 4, hipMemcpyDeviceToHost, h->stream));
         OPOSE_HIP_CHECK(hipMemcpyAsync(loss, sd, (size_t)n_cand * 8, hipMemcpyDeviceToHost, h->stream));
-        OPOSE_HIP_CHECK(hipMemcpyAsync(winner, best, 16, hipMemcpyDeviceToHost, h->stream));
-        OPOSE_HIP_CHECK(hipMemcpyAsync(win_loss, best + 16, 8, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(winner, w.best, 16, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(win_loss, w.loss, 8, hipMemcpyDeviceToHost, h->stream));
         OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
         h->prof_drain();
     });
@@ -300,68 +290,9 @@ int opose_debug_shapelet_score(opose_t* h, const float* min2, int n_cand, int n_
 int opose_shapelet_find(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int m,
                         const uint8_t* labels, int n_labels, int max_cands, int32_t* best, double* best_loss,
                         float* dis, int32_t* locs, int32_t* cand_num, double* cand_loss, int flags) {
-    if (!h || !seq || !off || !labels || !best || !best_loss || !dis || !locs) return OPOSE_E_ARG;
-    if (max_cands < 0 || (cand_num == nullptr) != (cand_loss == nullptr)) return OPOSE_E_ARG;
-    int negs = 0;
-    if (const int rc = shp_labels_check(h, labels, n_labels, n_seq, &negs)) return rc;
-    if (negs == n_labels) {
-        h->err = "shapelet: no positive sequence, so no candidate";
-        return OPOSE_E_ARG;
-    }
-    if (const int rc = shp_check(h, off, n_seq, D, m)) return rc;
-    OPOSE_TRY(h, {
-        enter_main(h);
-        const bool od = flags & OPOSE_OUT_DEVICE;
-        const int64_t L = off[n_seq];
-        std::vector<int> cands;
-        for (int i = 0; i < n_labels; ++i)
-            if (labels[i]) cands.push_back(i);
-        std::vector<ShpBlock> blocks;
-        std::vector<ShpChunk> chunks;
-        const int64_t total = shp_table(off, m, cands, max_cands ? max_cands : kShpDefaultCands, blocks, chunks);
-        if (total > INT32_MAX) throw std::invalid_argument("shapelet: too many candidates for one call");
-        int cap = 0;
-        for (const ShpChunk& c : chunks) cap = std::max(cap, c.nc);
-        const float* sd = shp_stage(h, h->shp_seq, seq, (size_t)L * D, flags & OPOSE_IN_DEVICE);
-        const int64_t* offd = shp_stage(h, h->shp_off, off, (size_t)n_seq + 1, false);
-        const uint8_t* yd = shp_stage(h, h->shp_labels, labels, (size_t)n_labels, false);
-        float* md = h->shp_min2.ensure<float>((size_t)cap * n_seq, h->stream);
-        int32_t* ld = h->shp_loc.ensure<int32_t>((size_t)cap * n_seq, h->stream);
-        // every candidate's num / loss when asked for, else one chunk's
-        const bool all = cand_num != nullptr;
-        int32_t* nd = all && od ? cand_num : h->shp_num.ensure<int32_t>(all ? (size_t)total : (size_t)cap, h->stream);
-        double* sl = all && od ? cand_loss : h->shp_loss.ensure<double>(all ? (size_t)total : (size_t)cap, h->stream);
-        uint8_t* wb = od ? nullptr : h->shp_best.ensure<uint8_t>(shp_best_bytes(n_seq), h->stream);
-        int32_t* bestd = od ? best : reinterpret_cast<int32_t*>(wb);
-        double* blossd = od ? best_loss : reinterpret_cast<double*>(wb + 16);
-        float* disd = od ? dis : reinterpret_cast<float*>(wb + 24);
-        int32_t* locsd = od ? locs : reinterpret_cast<int32_t*>(wb + 24 + 4 * (size_t)n_seq);
-        const ShpBlock* bd = shp_upload(h, h->shp_blocks, blocks);
-        size_t done = 0;
-        for (size_t ci = 0; ci < chunks.size(); ++ci) {
-            const ShpChunk& c = chunks[ci];
-            int32_t* cn = nd + (all ? done : 0);
-            double* cl = sl + (all ? done : 0);
-            run_mindist(h, sd, offd, n_seq, D, m, bd + c.b0, c.nb, c.nc, L, md, ld);
-            run_score(h, md, c.nc, n_seq, n_labels, yd, negs, cn, cl);
-            run_select(h, cn, cl, c.nc, bd + c.b0, c.nb, md, ld, n_seq, ci == 0, bestd, blossd, disd, locsd);
-            done += (size_t)c.nc;
-        }
-        if (!od) {
-            OPOSE_HIP_CHECK(hipMemcpyAsync(best, wb, 16, hipMemcpyDeviceToHost, h->stream));
-            OPOSE_HIP_CHECK(hipMemcpyAsync(best_loss, wb + 16, 8, hipMemcpyDeviceToHost, h->stream));
-            OPOSE_HIP_CHECK(hipMemcpyAsync(dis, wb + 24, 4 * (size_t)n_seq, hipMemcpyDeviceToHost, h->stream));
-            OPOSE_HIP_CHECK(hipMemcpyAsync(locs, wb + 24 + 4 * (size_t)n_seq, 4 * (size_t)n_seq, hipMemcpyDeviceToHost,
-                                           h->stream));
-            if (all) {
-                OPOSE_HIP_CHECK(hipMemcpyAsync(cand_num, nd, (size_t)total * 4, hipMemcpyDeviceToHost, h->stream));
-                OPOSE_HIP_CHECK(hipMemcpyAsync(cand_loss, sl, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream));
-            }
-            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
-        }
-        h->prof_drain();
-    });
-    return OPOSE_OK;
+    const int32_t one = m;
+    return opose_shapelet_find_lengths(h, seq, off, n_seq, D, &one, 1, labels, n_labels, max_cands, best, best_loss, dis,
+                                       locs, cand_num, cand_loss, flags);
 }
 
 int opose_shapelet_mindist_lengths(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D,
@@ -399,7 +330,7 @@ int opose_shapelet_mindist_lengths(opose_t* h, const float* seq, const int64_t* 
         int32_t* ld = od ? loc : h->shp_loc.ensure<int32_t>(n_out, h->stream);
         const ShpBlock* bd = shp_upload(h, h->shp_blocks, blocks);
         const ShpLenRows* rd = shp_upload(h, h->shp_lrows, rows);
-        run_mindist_lengths(h, sd, offd, n_seq, D, lens, bd, rd, (int)blocks.size(), (int)nc0, L, md, ld);
+        run_mindist(h, sd, offd, n_seq, D, lens, bd, rd, (int)blocks.size(), (int)nc0, L, md, ld);
         if (!od) {
             OPOSE_HIP_CHECK(hipMemcpyAsync(min2, md, n_out * 4, hipMemcpyDeviceToHost, h->stream));
             OPOSE_HIP_CHECK(hipMemcpyAsync(loc, ld, n_out * 4, hipMemcpyDeviceToHost, h->stream));
@@ -478,20 +409,16 @@ int opose_shapelet_find_lengths(opose_t* h, const float* seq, const int64_t* off
         const size_t n_score = all ? first_out[nl] : nl * cap;
         int32_t* nd = all && od ? cand_num : h->shp_num.ensure<int32_t>(n_score, h->stream);
         double* sl = all && od ? cand_loss : h->shp_loss.ensure<double>(n_score, h->stream);
-        // the winners when the outputs are host memory:
-        // int32 best[n_lens][4] | double best_loss[n_lens] | float dis[n_lens][n_seq] | int32 locs[n_lens][n_seq]
-        uint8_t* wb = od ? nullptr : h->shp_best.ensure<uint8_t>(nl * shp_best_bytes(n_seq), h->stream);
-        int32_t* bestd = od ? best : reinterpret_cast<int32_t*>(wb);
-        double* blossd = od ? best_loss : reinterpret_cast<double*>(wb + 16 * nl);
-        float* disd = od ? dis : reinterpret_cast<float*>(wb + 24 * nl);
-        int32_t* locsd = od ? locs : reinterpret_cast<int32_t*>(wb + 24 * nl + 4 * nl * ns);
+        const ShpWinners w =
+            od ? ShpWinners{nl, ns, best, best_loss, dis, locs}
+               : ShpWinners::in_block(h->shp_best.ensure<uint8_t>(ShpWinners::bytes(nl, ns), h->stream), nl, ns);
         const ShpBlock* bd = shp_upload(h, h->shp_blocks, blocks);
         const ShpLenRows* rd = shp_upload(h, h->shp_lrows, rows);
         const ShpBlock* seld = shp_upload(h, h->shp_sel, sel);
         std::vector<size_t> done(nl, 0);
         for (size_t ci = 0; ci < chunks.size(); ++ci) {
             const ShpChunk& c = chunks[ci];
-            run_mindist_lengths(h, sd, offd, n_seq, D, lens, bd + c.b0, rd + (size_t)c.b0 * nl, c.nb, c.nc, L, md, ld);
+            run_mindist(h, sd, offd, n_seq, D, lens, bd + c.b0, rd + (size_t)c.b0 * nl, c.nb, c.nc, L, md, ld);
             for (size_t l = 0; l < nl; ++l) {
                 const Part& p = parts[ci * nl + l];
                 if (!p.nc) continue;  // only tail starts in this chunk: the length keeps its winner
@@ -499,16 +426,13 @@ int opose_shapelet_find_lengths(opose_t* h, const float* seq, const int64_t* off
                 int32_t* cn = nd + (all ? first_out[l] + done[l] : l * cap);
                 double* cl = sl + (all ? first_out[l] + done[l] : l * cap);
                 run_score(h, ml, p.nc, n_seq, n_labels, yd, negs, cn, cl);
-                run_select(h, cn, cl, p.nc, seld + p.t0, p.nt, ml, ld + l * cap * ns, n_seq, done[l] == 0, bestd + 4 * l,
-                           blossd + l, disd + l * ns, locsd + l * ns);
+                run_select(h, cn, cl, p.nc, seld + p.t0, p.nt, ml, ld + l * cap * ns, n_seq, done[l] == 0, w.best + 4 * l,
+                           w.loss + l, w.dis + l * ns, w.locs + l * ns);
                 done[l] += (size_t)p.nc;
             }
         }
         if (!od) {
-            OPOSE_HIP_CHECK(hipMemcpyAsync(best, bestd, 16 * nl, hipMemcpyDeviceToHost, h->stream));
-            OPOSE_HIP_CHECK(hipMemcpyAsync(best_loss, blossd, 8 * nl, hipMemcpyDeviceToHost, h->stream));
-            OPOSE_HIP_CHECK(hipMemcpyAsync(dis, disd, 4 * nl * ns, hipMemcpyDeviceToHost, h->stream));
-            OPOSE_HIP_CHECK(hipMemcpyAsync(locs, locsd, 4 * nl * ns, hipMemcpyDeviceToHost, h->stream));
+            w.to_host(h, best, best_loss, dis, locs);
             if (all) {
                 OPOSE_HIP_CHECK(hipMemcpyAsync(cand_num, nd, first_out[nl] * 4, hipMemcpyDeviceToHost, h->stream));
                 OPOSE_HIP_CHECK(hipMemcpyAsync(cand_loss, sl, first_out[nl] * 8, hipMemcpyDeviceToHost, h->stream));

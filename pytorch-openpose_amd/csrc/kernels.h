@@ -185,16 +185,12 @@ void launch_motion_features(const double* motion, int64_t L, int joints, const i
                             int32_t* carry, float* out, hipStream_t st);
 void launch_sliding_distance(const float* pat, int m, const float* seq, const int64_t* off, int n_seq, int D, int64_t L,
                              float* dist, hipStream_t st);
-// min2 / loc [rows][n_seq]: table entry b writes rows out0 .. out0 + nvalid - 1
-void launch_shapelet_mindist(const float* seq, const int64_t* off, int n_seq, int D, int m, const ShpBlock* blocks,
-                             int n_blocks, float* min2, int32_t* loc, hipStream_t st);
-// the same for every length of `lens` in one pass over shared distances: `blocks` is the table of
-// the shortest length, rows [n_blocks][lens.n] gives each (entry, length) its first output row and
-// its count of valid starts.  Dynamic LDS of shapelet_lengths_lds_bytes(longest length) bytes.
-size_t shapelet_lengths_lds_bytes(int m_max);
-void launch_shapelet_mindist_lengths(const float* seq, const int64_t* off, int n_seq, int D, const ShpLens& lens,
-                                     const ShpBlock* blocks, const ShpLenRows* rows, int n_blocks, float* min2,
-                                     int32_t* loc, hipStream_t st);
+// min2 / loc [rows][n_seq] for every length of `lens` (one or more) in one pass over shared
+// distances: `blocks` is the table of the shortest length, rows [n_blocks][lens.n] gives each
+// (entry, length) its first output row and its count of valid starts
+void launch_shapelet_mindist(const float* seq, const int64_t* off, int n_seq, int D, const ShpLens& lens,
+                             const ShpBlock* blocks, const ShpLenRows* rows, int n_blocks, float* min2, int32_t* loc,
+                             hipStream_t st);
 void launch_shapelet_score(const float* min2, int n_cand, int n_seq, int n_labels, const uint8_t* labels, int negs,
                            int32_t* num, double* loss, hipStream_t st);
 void launch_shapelet_select(const int32_t* num, const double* loss, int n_cand, const ShpBlock* blocks, int n_blocks,

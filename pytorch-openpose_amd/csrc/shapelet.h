@@ -18,7 +18,7 @@ constexpr int kShpTC = 32;
 constexpr int kShpDC = 16;
 constexpr int kShpThreads = 256;
 constexpr int kShpSub = kShpThreads / kShpTR;  // threads sharing one candidate start's positions
-// shapelet_mindist_lengths: window lengths one call may share its distances among
+// window lengths one call may share its distances among
 constexpr int kShpMaxLens = 16;
 // opose_shapelet_find: candidates per chunk when the caller passes max_cands = 0
 constexpr int kShpDefaultCands = 2048;
@@ -49,7 +49,7 @@ struct ShpBlock {
     int32_t seq, r0, nvalid, out0;
 };
 
-// shapelet_mindist_lengths: the ascending window lengths, passed by value as a kernel argument
+// shapelet_mindist: the ascending window lengths, passed by value as a kernel argument
 struct ShpLens {
     int32_t n;
     int32_t m[kShpMaxLens];

@@ -7,7 +7,8 @@
 //    CorrespondingValue, the nose-neck scale)        => feat_blocklast, feat_carry, feat_compute
 //  * srcmx/utilmx.py:330-372             SlidingDistance(_torch)          => sliding_distance
 //  * srcmx/utilmx.py:375-391 + srcmx/shapeletmodel.py:140-152  matrixprofile_torch and the
-//    per-sample torch.min                                                 => shapelet_mindist
+//    per-sample torch.min, for every window length of srcmx/shapeletlearning.py:123-175's loop at
+//    once                                                                 => shapelet_mindist
 //  * srcmx/shapeletmodel.py:157-209      Bipartition_score, the loss and the best-candidate update
 //                                                                         => shapelet_score, shapelet_select
 //  * srcmx/DataAugmentation.py:106-150   AugmentateOneShapelet's sliding distances, hits below
@@ -205,27 +206,41 @@ void launch_sliding_distance(const float* pat, int m, const float* seq, const in
 }
 
 // ------------------------------------------------------------------------------------ mindist mode
-// Workgroup (block table entry, target sequence j): min over c of s(r, c) and its first c, for the
-// entry's candidate starts r.  Per block of kShpTC target positions:
+// shapelet_mindist, workgroup (block table entry, target sequence j): for the entry's candidate
+// starts r and each window length m_0 < m_1 < ... < m_{n-1} of `lens` (1 <= n <= kShpMaxLens), the
+// min over c of s(r, c) and its first c.  Per block of kShpTC target positions:
 //   1. E[a][q] = e(a, a + q - (kShpTR - 1)) for the rows a of the candidate window rows and the
 //      diagonals q that the tile's outputs use -- a band, not the square -- accumulated in LDS while
 //      D streams through the staging tiles xs / ys in chunks of kShpDC, d ascending;
-//   2. s(r, c) = E[r][q] + E[r+1][q] + ... along its diagonal, k ascending, against the running
-//      (min, loc) that a thread keeps in registers for its positions c = sub, sub + kShpSub, ...
-// Position blocks ascend, so a strict < keeps a thread's first minimum; the kShpSub partial results
-// of a start are merged on (bits, loc).  No atomics: a result does not depend on scheduling.
-constexpr int kShpNA = kShpTR + kShpMaxM - 1;  // candidate rows a workgroup may touch
-constexpr int kShpNB = kShpTC + kShpMaxM - 1;  // target rows of one position block
-constexpr int kShpND = kShpTR + kShpTC - 1;    // diagonals of a tile
+//   2. s(r, c) = E[r][q] + E[r+1][q] + ... along its diagonal, k ascending from +0, one walk per
+//      (start, position) for every length: E does not depend on m, so the partial sum after m_l
+//      terms is, bit for bit, the s of length m_l, a snapshot compared against that length's
+//      running (min, loc), which a thread keeps in registers for its positions c = sub,
+//      sub + kShpSub, ...
+// The block table is that of m_0, which has the most starts, and the band is sized for m_{n-1}; a
+// start or position is compared at length m_l only when its m_l rows lie within its clip
+// (blk.r0 + r + m_l <= len_i, c0 + c + m_l <= len_j), and as the lengths ascend the first that does
+// not fit ends the walk, so no E entry beyond the two clips is read.  Position blocks ascend, so a
+// strict < keeps a thread's first minimum.  The running pairs are kShpMaxLens scalars per thread
+// (the loops over l are fully unrolled: never an indexed array); the kShpSub threads of a start
+// are neighbouring lanes and merge on (bits, loc) by lane exchange.  No atomics: a result does not
+// depend on scheduling.  Length l's rows go to rows[entry][l].out0 .. of min2 / loc.  LDS is
+// dynamic: E [na][kShpND], xs [na][kShpDC + 1], ys [nb][kShpDC + 1] with na = kShpTR + m_max - 1,
+// nb = kShpTC + m_max - 1.
+constexpr int kShpND = kShpTR + kShpTC - 1;  // diagonals of a tile
+constexpr size_t shp_lds_bytes(int m_max) {
+    const int na = kShpTR + m_max - 1, nb = kShpTC + m_max - 1;
+    return sizeof(float) * ((size_t)na * kShpND + (size_t)(na + nb) * (kShpDC + 1));
+}
 static_assert(kShpThreads == kShpTR * kShpSub, "threads = starts x sub-positions");
-static_assert((kShpNA * kShpND + (kShpNA + kShpNB) * (kShpDC + 1)) * 4 <= 65536, "static LDS");
+static_assert(kShpSub <= 64 && (kShpSub & (kShpSub - 1)) == 0 && 64 % kShpSub == 0, "a start's threads share a wave");
+static_assert(shp_lds_bytes(kShpMaxM) <= 65536, "dynamic LDS within what a launch gets without an attribute call");
 
-// Step 1 of a position block, shared by shapelet_mindist and shapelet_mindist_lengths: the band E
-// (na rows of kShpND diagonals) of candidate rows xo .. xo + xrows - 1 against target rows
-// yo + c0 .. (nb of them, as far as the target's ylen rows reach), through the staging tiles xs
-// [na][kShpDC + 1] and ys [nb][kShpDC + 1].  An entry is accumulated by one thread, d ascending; an
-// entry of a row beyond xrows or ylen stays +0 and no row outside the two clips is read.  Ends
-// before the barrier that makes E visible.
+// Step 1 of a position block: the band E (na rows of kShpND diagonals) of candidate rows
+// xo .. xo + xrows - 1 against target rows yo + c0 .. (nb of them, as far as the target's ylen rows
+// reach), through the staging tiles xs [na][kShpDC + 1] and ys [nb][kShpDC + 1].  An entry is
+// accumulated by one thread, d ascending; an entry of a row beyond xrows or ylen stays +0 and no
+// row outside the two clips is read.  Ends before the barrier that makes E visible.
 __device__ inline void shp_fill_band(float* __restrict__ E, float* __restrict__ xs, float* __restrict__ ys,
                                      const float* __restrict__ seq, int64_t xo, int xrows, int64_t yo, int ylen,
                                      int c0, int na, int nb, int D, int t) {
@@ -258,82 +273,7 @@ __device__ inline void shp_fill_band(float* __restrict__ E, float* __restrict__ 
     }
 }
 
-__global__ __launch_bounds__(kShpThreads) void shapelet_mindist(const float* __restrict__ seq,
-                                                                const int64_t* __restrict__ off, int n_seq, int D, int m,
-                                                                const ShpBlock* __restrict__ blocks,
-                                                                float* __restrict__ min2, int32_t* __restrict__ loc) {
-    __shared__ float E[kShpNA * kShpND];
-    __shared__ float xs[kShpNA * (kShpDC + 1)];
-    __shared__ float ys[kShpNB * (kShpDC + 1)];
-    const int t = threadIdx.x, j = blockIdx.y;
-    const ShpBlock blk = blocks[blockIdx.x];
-    const int64_t xo = off[blk.seq] + blk.r0;  // the window rows of the entry's starts: xo .. xo + xrows - 1
-    const int xrows = blk.nvalid + m - 1;
-    const int64_t yo = off[j];
-    const int ylen = (int)(off[j + 1] - yo), P = ylen - m + 1;
-    const int na = kShpTR + m - 1, nb = kShpTC + m - 1;
-    const int r = t / kShpSub, sub = t % kShpSub;
-    uint32_t best = 0xffffffffu;
-    int bloc = 0;
-    for (int c0 = 0; c0 < P; c0 += kShpTC) {
-        shp_fill_band(E, xs, ys, seq, xo, xrows, yo, ylen, c0, na, nb, D, t);
-        __syncthreads();
-        if (r < blk.nvalid) {
-            for (int c = sub; c < kShpTC && c0 + c < P; c += kShpSub) {
-                const float* diag = E + r * kShpND + (c - r + kShpTR - 1);
-                float acc = 0.0f;
-                for (int k = 0; k < m; ++k) acc = acc + diag[k * kShpND];
-                const uint32_t bits = __float_as_uint(acc);
-                if (bits < best) {
-                    best = bits;
-                    bloc = c0 + c;
-                }
-            }
-        }
-        __syncthreads();  // E is zeroed next
-    }
-    uint32_t* pb = reinterpret_cast<uint32_t*>(xs);
-    int* pl = reinterpret_cast<int*>(ys);
-    pb[t] = best;
-    pl[t] = bloc;
-    __syncthreads();
-    if (sub == 0 && r < blk.nvalid) {
-        for (int s = 1; s < kShpSub; ++s) {
-            const uint32_t ob = pb[t + s];
-            const int ol = pl[t + s];
-            if (ob < best || (ob == best && ol < bloc)) {
-                best = ob;
-                bloc = ol;
-            }
-        }
-        const size_t o = (size_t)(blk.out0 + r) * n_seq + j;
-        min2[o] = __uint_as_float(best);
-        loc[o] = bloc;
-    }
-}
-
-void launch_shapelet_mindist(const float* seq, const int64_t* off, int n_seq, int D, int m, const ShpBlock* blocks,
-                             int n_blocks, float* min2, int32_t* loc, hipStream_t st) {
-    hipLaunchKernelGGL(shapelet_mindist, dim3(n_blocks, n_seq), dim3(kShpThreads), 0, st, seq, off, n_seq, D, m, blocks,
-                       min2, loc);
-}
-
-// ------------------------------------------------------------------------------------ several lengths
-// shapelet_mindist for the window lengths m_0 < m_1 < ... < m_{n-1} of `lens` at once.  E does not
-// depend on m, and the walk of s(r, c) runs k ascending from +0, so its partial sum after m_l terms
-// is, bit for bit, the s of length m_l: one band (sized for m_max = m_{n-1}) and one walk per
-// (start, position) serve every length, each a snapshot compared against its own running
-// (min, loc).  The block table is that of m_0, which has the most starts; a start or position is
-// compared at length m_l only when its m_l rows lie within its clip (blk.r0 + r + m_l <= len_i,
-// c0 + c + m_l <= len_j), and as the lengths ascend the first that does not fit ends the walk, so
-// no E entry beyond the two clips is read.  The running pairs are kShpMaxLens scalars per thread
-// (the loops over l are fully unrolled: never an indexed array), the kShpSub threads of a start
-// are neighbouring lanes and merge on (bits, loc) by lane exchange, and length l's rows go to
-// rows[entry][l].out0 .. of min2 / loc.  LDS is dynamic: E [na][kShpND], xs [na][kShpDC + 1],
-// ys [nb][kShpDC + 1] with na = kShpTR + m_max - 1, nb = kShpTC + m_max - 1.
-static_assert(kShpSub <= 64 && (kShpSub & (kShpSub - 1)) == 0 && 64 % kShpSub == 0, "a start's threads share a wave");
-
-__global__ __launch_bounds__(kShpThreads) void shapelet_mindist_lengths(
+__global__ __launch_bounds__(kShpThreads) void shapelet_mindist(
     const float* __restrict__ seq, const int64_t* __restrict__ off, int n_seq, int D, const ShpLens lens,
     const ShpBlock* __restrict__ blocks, const ShpLenRows* __restrict__ rows, float* __restrict__ min2,
     int32_t* __restrict__ loc) {
@@ -408,17 +348,11 @@ __global__ __launch_bounds__(kShpThreads) void shapelet_mindist_lengths(
     }
 }
 
-size_t shapelet_lengths_lds_bytes(int m_max) {
-    const int na = kShpTR + m_max - 1, nb = kShpTC + m_max - 1;
-    return sizeof(float) * ((size_t)na * kShpND + (size_t)(na + nb) * (kShpDC + 1));
-}
-
-void launch_shapelet_mindist_lengths(const float* seq, const int64_t* off, int n_seq, int D, const ShpLens& lens,
-                                     const ShpBlock* blocks, const ShpLenRows* rows, int n_blocks, float* min2,
-                                     int32_t* loc, hipStream_t st) {
-    hipLaunchKernelGGL(shapelet_mindist_lengths, dim3(n_blocks, n_seq), dim3(kShpThreads),
-                       shapelet_lengths_lds_bytes(lens.m[lens.n - 1]), st, seq, off, n_seq, D, lens, blocks, rows, min2,
-                       loc);
+void launch_shapelet_mindist(const float* seq, const int64_t* off, int n_seq, int D, const ShpLens& lens,
+                             const ShpBlock* blocks, const ShpLenRows* rows, int n_blocks, float* min2, int32_t* loc,
+                             hipStream_t st) {
+    hipLaunchKernelGGL(shapelet_mindist, dim3(n_blocks, n_seq), dim3(kShpThreads), shp_lds_bytes(lens.m[lens.n - 1]), st,
+                       seq, off, n_seq, D, lens, blocks, rows, min2, loc);
 }
 
 // ------------------------------------------------------------------------------------ score

@@ -106,20 +106,45 @@ def SlidingDistance(pattern, sequence, handle=None):
     return out
 
 
+def _lengths(m_lens) -> np.ndarray:
+    return np.ascontiguousarray([int(m) for m in m_lens], np.int32)
+
+
+def _labels(labels) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(labels.cpu() if hasattr(labels, "cpu") else labels) != 0, np.uint8)
+
+
+def _n_cand(off, seqs, m) -> int:
+    """The candidate starts of the sequences `seqs` at window length m (those outside the batch,
+    which the library refuses, count none)."""
+    return int(sum(max(int(off[i + 1] - off[i]) - int(m) + 1, 0) for i in seqs if 0 <= i < len(off) - 1))
+
+
+def _empty(dev, like, shape, np_dtype):
+    import torch
+    if dev:
+        return torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=like.device)
+    return np.empty(shape, np_dtype)
+
+
+def _find_outputs(dev, like, lead, n_seq, n_cand, every):
+    """The outputs of a find call, with leading dimensions `lead` (() or (n_lens,)): best lead + (4,),
+    loss lead + (1,), dis and locs lead + (n_seq,), and nums / losses [n_cand] (None unless every)."""
+    best, loss = _empty(dev, like, lead + (4,), np.int32), _empty(dev, like, lead + (1,), np.float64)
+    dis, locs = _empty(dev, like, lead + (n_seq,), np.float32), _empty(dev, like, lead + (n_seq,), np.int32)
+    nums = _empty(dev, like, n_cand, np.int32) if every else None
+    losses = _empty(dev, like, n_cand, np.float64) if every else None
+    return best, loss, dis, locs, nums, losses
+
+
 def shapelet_mindist(seq, off, m, cand_seqs, handle=None):
     """The first stage alone on a ragged batch: (min2, loc) [n_cand, n_seq] (opose_shapelet_mindist)."""
-    import torch
     dev = _is_dev(seq)
     off = np.ascontiguousarray(off, np.int64)
     cs = np.ascontiguousarray(cand_seqs, np.int32)
-    n_seq = len(off) - 1
-    n_cand = int(sum(max(int(off[i + 1] - off[i]) - m + 1, 0) for i in cs if 0 <= i < n_seq))
+    n_seq, n_cand = len(off) - 1, _n_cand(off, cs, m)
     h = handle or default_handle(seq.device.index if dev else 0)
-    if dev:
-        min2 = torch.empty((n_cand, n_seq), dtype=torch.float32, device=seq.device)
-        loc = torch.empty((n_cand, n_seq), dtype=torch.int32, device=seq.device)
-    else:
-        min2, loc = np.empty((n_cand, n_seq), np.float32), np.empty((n_cand, n_seq), np.int32)
+    min2, loc = _empty(dev, seq, (n_cand, n_seq), np.float32), _empty(dev, seq, (n_cand, n_seq), np.int32)
     _run(h, dev, lib.opose_shapelet_mindist, _native._ptr(seq), off.ctypes.data, n_seq, seq.shape[1], int(m),
          cs.ctypes.data, len(cs), _native._ptr(min2), _native._ptr(loc), _native.DEVICE_IO if dev else 0)
     return min2, loc
@@ -128,38 +153,18 @@ def shapelet_mindist(seq, off, m, cand_seqs, handle=None):
 def shapelet_find(seq, off, labels, m, max_cands=0, every=False, handle=None):
     """opose_shapelet_find on a ragged batch: a dict of best [4], loss, dis [n_seq], locs [n_seq] (and,
     with every=True, every candidate's num and loss).  Device inputs give device outputs."""
-    import torch
     dev = _is_dev(seq)
     off = np.ascontiguousarray(off, np.int64)
-    lab = np.ascontiguousarray(np.asarray(labels.cpu() if hasattr(labels, "cpu") else labels) != 0, np.uint8)
+    lab = _labels(labels)
     n_seq, n = len(off) - 1, len(lab)
-    n_cand = int(sum(max(int(off[i + 1] - off[i]) - m + 1, 0) for i in range(min(n, n_seq)) if lab[i]))
+    n_cand = _n_cand(off, np.nonzero(lab)[0], m)
     h = handle or default_handle(seq.device.index if dev else 0)
-    if dev:
-        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=seq.device)  # noqa: E731
-        best, loss = mk(4, torch.int32), mk(1, torch.float64)
-        dis, locs = mk(n_seq, torch.float32), mk(n_seq, torch.int32)
-        nums, losses = (mk(n_cand, torch.int32), mk(n_cand, torch.float64)) if every else (None, None)
-    else:
-        best, loss = np.empty(4, np.int32), np.empty(1, np.float64)
-        dis, locs = np.empty(n_seq, np.float32), np.empty(n_seq, np.int32)
-        nums, losses = (np.empty(n_cand, np.int32), np.empty(n_cand, np.float64)) if every else (None, None)
+    best, loss, dis, locs, nums, losses = _find_outputs(dev, seq, (), n_seq, n_cand, every)
     _run(h, dev, lib.opose_shapelet_find, _native._ptr(seq), off.ctypes.data, n_seq, seq.shape[1], int(m),
          lab.ctypes.data, n, int(max_cands), _native._ptr(best), _native._ptr(loss), _native._ptr(dis),
          _native._ptr(locs), _native._ptr(nums) if every else None, _native._ptr(losses) if every else None,
          _native.DEVICE_IO if dev else 0)
     return {"best": best, "loss": loss, "dis": dis, "locs": locs, "nums": nums, "losses": losses}
-
-
-def _lengths(m_lens) -> np.ndarray:
-    return np.ascontiguousarray([int(m) for m in m_lens], np.int32)
-
-
-def _empty(dev, like, shape, np_dtype):
-    import torch
-    if dev:
-        return torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=like.device)
-    return np.empty(shape, np_dtype)
 
 
 def shapelet_mindist_lengths(seq, off, m_lens, cand_seqs, handle=None):
@@ -171,14 +176,13 @@ def shapelet_mindist_lengths(seq, off, m_lens, cand_seqs, handle=None):
     cs = np.ascontiguousarray(cand_seqs, np.int32)
     ml = _lengths(m_lens)
     n_seq = len(off) - 1
-    counts = [int(sum(max(int(off[i + 1] - off[i]) - int(m) + 1, 0) for i in cs if 0 <= i < n_seq)) for m in ml]
-    total = sum(counts)
+    starts = np.concatenate(([0], np.cumsum([_n_cand(off, cs, m) for m in ml], dtype=np.int64)))
     h = handle or default_handle(seq.device.index if dev else 0)
-    min2, loc = _empty(dev, seq, (total, n_seq), np.float32), _empty(dev, seq, (total, n_seq), np.int32)
+    shape = (int(starts[-1]), n_seq)
+    min2, loc = _empty(dev, seq, shape, np.float32), _empty(dev, seq, shape, np.int32)
     _run(h, dev, lib.opose_shapelet_mindist_lengths, _native._ptr(seq), off.ctypes.data, n_seq, seq.shape[1],
          ml.ctypes.data, len(ml), cs.ctypes.data, len(cs), _native._ptr(min2), _native._ptr(loc),
          _native.DEVICE_IO if dev else 0)
-    starts = np.concatenate(([0], np.cumsum(counts)))
     return [(min2[a:b], loc[a:b]) for a, b in zip(starts[:-1], starts[1:])]
 
 
@@ -187,22 +191,16 @@ def shapelet_find_lengths(seq, off, labels, m_lens, max_cands=0, every=False, ha
     shapelet_find returns (views of the call's output buffers).  Device inputs give device outputs."""
     dev = _is_dev(seq)
     off = np.ascontiguousarray(off, np.int64)
-    lab = np.ascontiguousarray(np.asarray(labels.cpu() if hasattr(labels, "cpu") else labels) != 0, np.uint8)
+    lab = _labels(labels)
     ml = _lengths(m_lens)
     n_seq, n, nl = len(off) - 1, len(lab), len(ml)
-    counts = [int(sum(max(int(off[i + 1] - off[i]) - int(m) + 1, 0) for i in range(min(n, n_seq)) if lab[i]))
-              for m in ml]
-    total = sum(counts)
+    starts = np.concatenate(([0], np.cumsum([_n_cand(off, np.nonzero(lab)[0], m) for m in ml], dtype=np.int64)))
     h = handle or default_handle(seq.device.index if dev else 0)
-    best, loss = _empty(dev, seq, (nl, 4), np.int32), _empty(dev, seq, (nl, 1), np.float64)
-    dis, locs = _empty(dev, seq, (nl, n_seq), np.float32), _empty(dev, seq, (nl, n_seq), np.int32)
-    nums = _empty(dev, seq, total, np.int32) if every else None
-    losses = _empty(dev, seq, total, np.float64) if every else None
+    best, loss, dis, locs, nums, losses = _find_outputs(dev, seq, (nl,), n_seq, int(starts[-1]), every)
     _run(h, dev, lib.opose_shapelet_find_lengths, _native._ptr(seq), off.ctypes.data, n_seq, seq.shape[1],
          ml.ctypes.data, nl, lab.ctypes.data, n, int(max_cands), _native._ptr(best), _native._ptr(loss),
          _native._ptr(dis), _native._ptr(locs), _native._ptr(nums) if every else None,
          _native._ptr(losses) if every else None, _native.DEVICE_IO if dev else 0)
-    starts = np.concatenate(([0], np.cumsum(counts)))
     return [{"best": best[l], "loss": loss[l], "dis": dis[l], "locs": locs[l],
              "nums": nums[starts[l]:starts[l + 1]] if every else None,
              "losses": losses[starts[l]:starts[l + 1]] if every else None} for l in range(nl)]

@@ -423,6 +423,53 @@ def test_find_chunk_cut_inside_a_candidate_block(sh, name):
         assert np.array_equal(one[k], cut[k]), k
 
 
+def test_single_length_rows_are_written_in_place_and_nothing_past_them(sh):
+    """opose_shapelet_mindist / opose_shapelet_find run the several-lengths kernel with one length, so
+    a start's output row comes from the per-(entry, length) row table, not from the block table's out0.
+    m = 5, D = kShpDC + 3, clips of one start, exactly one table entry, an entry with a single start
+    behind a full one, and one with two; every clip a candidate; max_cands = 8, so chunks end inside
+    table entries.  The device outputs are prefilled and kShpThreads elements too long: every row
+    equals the statement bit for bit and nothing past the end is written."""
+    from src import _native
+    lib, handle = _native.lib, sh.default_handle()
+    m, D = 5, DC + 3
+    seqs = random_seqs(97, [m, m + TR - 1, m + TR, m + TR + 1], D)
+    labels = np.ones(len(seqs), np.uint8)
+    want = sc.find(seqs, labels, m)  # its min2 / loc: sc.mindist with every clip a candidate
+    seq, off = ragged(seqs)
+    n_seq, n_cand = len(seqs), 1 + TR + (TR + 1) + (TR + 2)
+    assert want["min2"].shape == (n_cand, n_seq) and 1 < 8 < 1 + TR  # the first chunk ends inside clip 1's entry
+    seqd = torch.from_numpy(seq).cuda()
+
+    def prefilled(n, dtype, fill):
+        return torch.full((n + T,), fill, dtype=dtype, device="cuda")
+
+    def written(buf, n, fill):
+        got = buf.cpu().numpy()
+        assert (got[n:] == fill).all()
+        return got[:n]
+
+    cs = np.arange(n_seq, dtype=np.int32)
+    min2, loc = prefilled(n_cand * n_seq, torch.float32, -1.0), prefilled(n_cand * n_seq, torch.int32, -7)
+    handle.torch_call(lib.opose_shapelet_mindist, seqd.data_ptr(), off.ctypes.data, n_seq, D, m, cs.ctypes.data, n_seq,
+                      min2.data_ptr(), loc.data_ptr(), _native.DEVICE_IO)
+    assert np.array_equal(bits(written(min2, n_cand * n_seq, -1.0)), bits(want["min2"]).reshape(-1))
+    assert np.array_equal(written(loc, n_cand * n_seq, -7), want["loc"].reshape(-1))
+
+    best, loss = prefilled(4, torch.int32, -7), prefilled(1, torch.float64, -1.0)
+    dis, locs = prefilled(n_seq, torch.float32, -1.0), prefilled(n_seq, torch.int32, -7)
+    nums, losses = prefilled(n_cand, torch.int32, -7), prefilled(n_cand, torch.float64, -1.0)
+    handle.torch_call(lib.opose_shapelet_find, seqd.data_ptr(), off.ctypes.data, n_seq, D, m, labels.ctypes.data, n_seq,
+                      8, best.data_ptr(), loss.data_ptr(), dis.data_ptr(), locs.data_ptr(), nums.data_ptr(),
+                      losses.data_ptr(), _native.DEVICE_IO)
+    assert np.array_equal(written(nums, n_cand, -7), want["nums"])
+    assert np.array_equal(written(losses, n_cand, -1.0).view(np.uint64), want["losses"].view(np.uint64))
+    assert written(best, 4, -7).tolist() == [want["shapeindex"], want["cand"], want["num"], n_cand]
+    assert written(loss, 1, -1.0)[0] == want["loss"]
+    assert np.array_equal(bits(written(dis, n_seq, -1.0)), bits(want["dis"]))
+    assert np.array_equal(written(locs, n_seq, -7), want["locs"])
+
+
 @pytest.mark.parametrize("joints", [18, 60])
 @pytest.mark.parametrize("name", sc.FEATURE_CASES)
 def test_feature_edges_equal_the_statement(sh, name, joints):

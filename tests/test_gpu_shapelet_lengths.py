@@ -1,9 +1,11 @@
-"""GPU: the search over several window lengths in one pass (shapelet_mindist_lengths in
-csrc/shapelet.hip, opose_shapelet_mindist_lengths / opose_shapelet_find_lengths, and their Python
-forms in src/shapelet.py) against the single-length entry points and the NumPy statement of
-tests/shapelet_lengths_cases.py.  Every comparison is bit equality.  The cases are those of
-shapelet_lengths_cases.py, cut to the constants of csrc/shapelet.h;
-tests/test_shapelet_lengths_cases.py shows on the CPU that each has the geometry it claims."""
+"""GPU: the search over several window lengths in one pass (shapelet_mindist in csrc/shapelet.hip
+with more than one length, opose_shapelet_mindist_lengths / opose_shapelet_find_lengths, and their
+Python forms in src/shapelet.py) against the NumPy statement of tests/shapelet_lengths_cases.py and
+against the single-length entry points, which launch the same kernel once per length: a snapshot
+taken at the wrong term, or a row of one length landing in another's, differs from both.  Every
+comparison is bit equality.  The cases are those of shapelet_lengths_cases.py, cut to the constants
+of csrc/shapelet.h; tests/test_shapelet_lengths_cases.py shows on the CPU that each has the
+geometry it claims."""
 import os
 import re
 
@@ -45,7 +47,7 @@ def ragged(seqs):
 
 def check_mindist_lengths(sh, seqs, m_lens, cands, want=None, single=True):
     """The several-lengths call against the statement (when given) and, per length, against the
-    single-length call on the device."""
+    single-length call on the device (the same kernel, launched with that length alone)."""
     seq, off = ragged(seqs)
     got = sh.shapelet_mindist_lengths(seq, off, m_lens, cands)
     assert len(got) == len(m_lens)
