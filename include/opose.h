@@ -36,6 +36,8 @@
  *   m_len loop                     .py:123-175               opose_shapelet_mindist_lengths
  *   DataAugmentation.              srcmx/DataAugmentation    opose_shapelet_scan;
  *   AugmentateOneShapelet          .py:78-153                opose_debug_shapelet_pick (the hit walk)
+ *   ShapeletNetModel (train,       srcmx/shapeletmodel.py:   opose_shapelet_net_train;
+ *   __call__, localizeshape)       11-90                     opose_debug_shapelet_net_grad (one backward)
  *
  * Conventions: plain pointers and sizes only; 0 = OK, negative = error (see opose_status).
  * Host pointers are caller-owned and read-only; the library copies them. A handle owns one
@@ -523,6 +525,73 @@ int opose_shapelet_scan(opose_t* h, const float* pat, const int64_t* pat_off, in
                         const float* seq, const int64_t* off, int n_seq, int D, int max_pats,
                         int64_t* occ_off, int32_t* occ_pos, float* occ_dist, int64_t cap, int flags);
 
+/* Learning shapelets by gradient descent (ShapeletNetModel, srcmx/shapeletmodel.py:11-90, the model of
+ * ShapeletsFinding's FindShaplets_Net_ED): n_models independent models over the same clips, each a
+ * query [m_k][D] and a Linear(1, 2) head, trained by Adam on the cross-entropy of the head applied
+ * to the clip's smallest squared sliding distance.  tests/shapelet_net_cases.py states the rule in
+ * NumPy.
+ *
+ * Inputs.  seq / off: a ragged batch as above; labels uint8 [n_seq], host memory, 0 / 1.
+ *   t_pad = 0: clip i has the positions c = 0 .. len_i - m_k, and every len_i >= m_k.
+ *   t_pad >= every len_i and every m_k: the reference's zero-padded [N][D][T = t_pad] batch without
+ *     materialising it: every clip has the positions c = 0 .. t_pad - m_k, a row at or past len_i
+ *     reads as +0, and len_i >= 0.
+ * The queries are concatenated, float32 [q_off[n_models]][D], ragged by q_off int64 [n_models + 1]
+ * (host memory), as the patterns of opose_shapelet_scan are; head float32 [n_models][4] holds
+ * (w0, w1, b0, b1) of each model's Linear(1, 2).
+ *
+ * Forward.  s_i(c) = sum over k ascending of ( sum over d ascending of (q[k][d] - x_i[c + k][d])^2 ),
+ * fp32, each sum from +0, one rounding per operation, no fused multiply-add: the direct form, not
+ * the reference's QQ + XX - 2 QX, which cancels.  d_i = the first minimum of s_i over c (strict <,
+ * c ascending), loc_i its c; no square root (the reference's model works on the squared distance).
+ * Given the same parameter bits, d_i and loc_i equal the NumPy statement's bit for bit.
+ *
+ * Head, per model, in float64 from the fp32 d_i, w, b, N = n_seq:
+ *   z_ij = w_j d_i + b_j;  log p_ij = z_ij - (mx + log(exp(z_i0 - mx) + exp(z_i1 - mx))), mx the
+ *   larger z;  loss = -(sum over i of log p_i[y_i]) / N;  dz_ij = (p_ij - [y_i = j]) / N;
+ *   g_i = dz_i0 w_0 + dz_i1 w_1;  dw_j = sum over i of dz_ij d_i;  db_j = sum over i of dz_ij
+ * every sum over i ascending from +0.  correct counts the clips with argmax_j z_ij == y_i, index 0
+ * on a tie (as torch.max).
+ *
+ * Query gradient, fp32: dq[k][d] = sum over i ascending of (float) g_i * (2 * (q[k][d] - x_i[loc_i + k][d])).
+ *
+ * Adam (torch.optim.Adam's defaults: betas 0.9 / 0.999, eps 1e-8, no weight decay), one step count t
+ * for all parameters, fp32 state, gradients rounded to fp32:
+ *   m = m + (g - m) * (float)(1 - 0.9);  v = v * 0.999f + ((float)(1 - 0.999) * g) * g
+ *   p = p - (float)(lr / (1 - 0.9^t)) * (m / (sqrt(v) / (float) sqrt(1 - 0.999^t) + 1e-8f))
+ * No floating-point atomics anywhere: every sum has one order and two runs give identical bits.
+ *
+ * The state is the caller's, in and out: query, head, and the first and second moments of both
+ * (q_m, q_v shaped like query; head_m, head_v like head; zero before the first step).  step0 is the
+ * number of steps the state has taken, epochs (>= 0) the steps of this call: epoch e (0-based) is a
+ * forward pass, the head with its update and the query update at t = step0 + e + 1, enqueued back
+ * to back with no host wait.  Because the caller owns all state, a call of a epochs followed by
+ * one of b epochs with step0 = a equals one call of a + b, bit for bit.
+ *
+ * Outputs, from a closing forward pass with the final parameters (what the reference's Net(X, Y)
+ * returns): dis float32 and locs int32 [n_models][n_seq], loss float64 [n_models], correct int32
+ * [n_models]; loss_hist float64 [n_models][epochs], each epoch's loss before its update, or NULL.
+ * OPOSE_IN_DEVICE: seq is device memory.  OPOSE_OUT_DEVICE: the state and the outputs are device
+ * memory and the call is asynchronous on the handle's stream; otherwise all are host memory.
+ *
+ * Checked before anything is launched, in this order:
+ *   1. OPOSE_E_ARG   a null handle or pointer (loss_hist may be null)
+ *   2. OPOSE_E_ARG   lr not above 0, epochs < 0, step0 < 0
+ *   3. OPOSE_E_ARG   n_seq < 1, D < 1, n_models < 1, t_pad < 0
+ *   4. OPOSE_E_SHAPE n_seq > 4096, D > 1024, n_models > 16
+ *   5. OPOSE_E_ARG   off does not start at 0 or decreases;  OPOSE_E_SHAPE L >= 2^31
+ *   6. OPOSE_E_ARG   q_off does not start at 0, or a query of no rows;  OPOSE_E_SHAPE a query of
+ *                    more than 128 rows
+ *   7. OPOSE_E_ARG   a label that is not 0 or 1
+ *   8. OPOSE_E_SHAPE t_pad = 0 and a clip shorter than the longest query; t_pad > 0 and below the
+ *                    longest clip or the longest query
+ * A refused call leaves the state and the outputs untouched. */
+int opose_shapelet_net_train(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int t_pad,
+                             const uint8_t* labels, const int64_t* q_off, int n_models, float* query, float* head,
+                             float* q_m, float* q_v, float* head_m, float* head_v, int64_t step0, int epochs,
+                             double lr, float* dis, int32_t* locs, double* loss, int32_t* correct,
+                             double* loss_hist, int flags);
+
 /* Hand on N crops uint8 [H][W][3] (util.handDetect gives squares): peaks [N][21][3]
  * (x, y, score), found [N][21] (0 = part missing, the reference's [0,0,0] row). */
 int opose_hand_infer(opose_t* h, const uint8_t* bgr, int N, int H, int W, int64_t row_stride,
@@ -753,6 +822,13 @@ int opose_debug_shapelet_score(opose_t* h, const float* min2, int n_cand, int n_
  * [n_seq + 1], occ_pos, occ_dist, cap and the return value as opose_shapelet_scan with host outputs. */
 int opose_debug_shapelet_pick(opose_t* h, const float* dist, const int64_t* off, int n_seq, int m, float sigma,
                               int64_t* occ_off, int32_t* occ_pos, float* occ_dist, int64_t cap);
+/* One backward pass of opose_shapelet_net_train for one model, with no update, on host arrays: for
+ * the query [m][D] and head [4] given, g float32 [n_seq], dq float32 [m][D], dhead float64 [4] =
+ * (dw0, dw1, db0, db1) and loss float64 [1] as that call's rule states them.  The batch, t_pad and
+ * labels, their checks and the order of the checks as there. */
+int opose_debug_shapelet_net_grad(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int t_pad,
+                                  const uint8_t* labels, const float* query, int m, const float* head, float* g,
+                                  float* dq, double* dhead, double* loss);
 
 #ifdef __cplusplus
 }

@@ -438,6 +438,9 @@ struct opose_ctx {
     // opose_shapelet_scan: the pattern table and window lengths, a chunk's distance rows and hit
     // masks, its per-pair counts, the running total, and the staged occurrence outputs
     opose::DevBuf scan_pats, scan_m, scan_dist, scan_mask, scan_counts, scan_total, scan_off, scan_pos, scan_odist;
+    // opose_shapelet_net_train: the model table, the two (distance, location) key buffers, g, the
+    // head's per-clip terms, and the staged state and outputs of a call on host memory
+    opose::DevBuf net_tab, net_best, net_g, net_ws, net_state, net_out;
     // opose_batch_hand_extract cuts its 2N crops into chunks the conv kernels can address (as
     // opose_hand_infer_crops does); OPOSE_EXTRACT_CHUNK=n at handle creation: n crops per chunk
     // instead (tests/test_gpu_hand_extract.py runs a small batch in two chunks)

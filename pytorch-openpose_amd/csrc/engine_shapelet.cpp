@@ -1,6 +1,7 @@
 // engine_shapelet.cpp — the shapelet search entry points: validation of the ragged batch, the block
 // table of the candidate starts, chunking, and the launches of shapelet.hip; and the scan of whole
-// streams for many patterns (its pattern table, chunks and occurrence outputs).
+// streams for many patterns (its pattern table, chunks and occurrence outputs); and the training of
+// the learned shapelet models (shapelet_net.hip: its checks, staged state and the epoch loop).
 #include "engine.h"
 
 namespace opose {
@@ -617,4 +618,223 @@ int opose_debug_shapelet_pick(opose_t* h, const float* dist, const int64_t* off,
         h->prof_drain();
     });
     return status;
+}
+
+// ------------------------------------------------------------------------------------ learned model
+namespace opose {
+
+// What a training call's kernels need of its geometry: the model table, the shortest and longest
+// query, and the forward grid's tiles (those of the most positions any clip and model have).
+struct NetGeom {
+    std::vector<NetModel> tab;
+    int m_min = 0, m_max = 0, tiles = 0;
+};
+
+// The checks of opose_shapelet_net_train after its pointers and scalars, in the order include/opose.h
+// documents.  Nothing is launched unless this returns OPOSE_OK.
+static int net_check(opose_ctx* h, const int64_t* off, int n_seq, int D, int t_pad, const uint8_t* labels,
+                     const int64_t* q_off, int n_models, NetGeom* g) {
+    if (n_seq < 1 || D < 1 || n_models < 1 || t_pad < 0) {
+        h->err = "shapelet net: n_seq, D and n_models must be positive and t_pad not negative";
+        return OPOSE_E_ARG;
+    }
+    if (n_seq > kShpMaxSeq || D > kShpMaxD || n_models > kNetMaxModels) {
+        h->err = "shapelet net: n_seq, D or n_models beyond the supported limit";
+        return OPOSE_E_SHAPE;
+    }
+    if (const int rc = scan_offsets_check(h, off, n_seq)) return rc;
+    if (off[n_seq] > kShpMaxRows) {
+        h->err = "shapelet net: too many rows";
+        return OPOSE_E_SHAPE;
+    }
+    if (q_off[0] != 0) {
+        h->err = "shapelet net: q_off must start at 0";
+        return OPOSE_E_ARG;
+    }
+    for (int k = 0; k < n_models; ++k)
+        if (q_off[k + 1] <= q_off[k]) {
+            h->err = "shapelet net: a query of no rows, or q_off decreases";
+            return OPOSE_E_ARG;
+        }
+    g->tab.resize(n_models);
+    g->m_min = kShpMaxM + 1;
+    g->m_max = 0;
+    for (int k = 0; k < n_models; ++k) {
+        const int64_t m = q_off[k + 1] - q_off[k];
+        if (m > kShpMaxM) {
+            h->err = "shapelet net: a query longer than the supported window";
+            return OPOSE_E_SHAPE;
+        }
+        g->tab[k] = NetModel{q_off[k], (int32_t)m, 0};
+        g->m_min = std::min(g->m_min, (int)m);
+        g->m_max = std::max(g->m_max, (int)m);
+    }
+    for (int i = 0; i < n_seq; ++i)
+        if (labels[i] > 1) {
+            h->err = "shapelet net: labels must be 0 or 1";
+            return OPOSE_E_ARG;
+        }
+    int64_t len_min = INT64_MAX, len_max = 0;
+    for (int i = 0; i < n_seq; ++i) {
+        len_min = std::min(len_min, off[i + 1] - off[i]);
+        len_max = std::max(len_max, off[i + 1] - off[i]);
+    }
+    if (t_pad == 0 && len_min < g->m_max) {
+        h->err = "shapelet net: a clip is shorter than a query (and t_pad is 0)";
+        return OPOSE_E_SHAPE;
+    }
+    if (t_pad != 0 && (t_pad < len_max || t_pad < g->m_max)) {
+        h->err = "shapelet net: t_pad is shorter than a clip or a query";
+        return OPOSE_E_SHAPE;
+    }
+    const int64_t p_max = (t_pad ? t_pad : len_max) - g->m_min + 1;
+    g->tiles = (int)((p_max + kNetTC - 1) / kNetTC);
+    return OPOSE_OK;
+}
+
+// Adam's two per-step scalars as torch forms them: in float64 from the step count, rounded once
+static void net_adam_scalars(double lr, int64_t t, float* step, float* bc2s) {
+    *step = (float)(lr / (1.0 - std::pow(0.9, (double)t)));
+    *bc2s = (float)std::sqrt(1.0 - std::pow(0.999, (double)t));
+}
+
+}  // namespace opose
+
+int opose_shapelet_net_train(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int t_pad,
+                             const uint8_t* labels, const int64_t* q_off, int n_models, float* query, float* head,
+                             float* q_m, float* q_v, float* head_m, float* head_v, int64_t step0, int epochs, double lr,
+                             float* dis, int32_t* locs, double* loss, int32_t* correct, double* loss_hist, int flags) {
+    if (!h || !seq || !off || !labels || !q_off || !query || !head || !q_m || !q_v || !head_m || !head_v || !dis ||
+        !locs || !loss || !correct)
+        return OPOSE_E_ARG;
+    if (!(lr > 0.0) || epochs < 0 || step0 < 0) {
+        h->err = "shapelet net: lr must be positive, epochs and step0 not negative";
+        return OPOSE_E_ARG;
+    }
+    NetGeom geo;
+    if (const int rc = net_check(h, off, n_seq, D, t_pad, labels, q_off, n_models, &geo)) return rc;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const bool od = flags & OPOSE_OUT_DEVICE;
+        const int64_t L = off[n_seq];
+        const size_t ns = (size_t)n_seq, nm = (size_t)n_models, nq = (size_t)q_off[n_models] * D, ne = (size_t)epochs;
+        // (every clip may be empty in the padded mode: then no row is ever addressed)
+        const float* sd = L ? shp_stage(h, h->shp_seq, seq, (size_t)L * D, flags & OPOSE_IN_DEVICE) : nullptr;
+        const int64_t* offd = shp_stage(h, h->shp_off, off, ns + 1, false);
+        const uint8_t* yd = shp_stage(h, h->shp_labels, labels, ns, false);
+        // the state: the caller's device arrays, or one staged block
+        //   float query[nq] | q_m[nq] | q_v[nq] | head[4 nm] | head_m[4 nm] | head_v[4 nm]
+        float* st[6] = {query, q_m, q_v, head, head_m, head_v};
+        float* const host_st[6] = {query, q_m, q_v, head, head_m, head_v};
+        const size_t st_n[6] = {nq, nq, nq, 4 * nm, 4 * nm, 4 * nm};
+        if (!od) {
+            float* p = h->net_state.ensure<float>(3 * nq + 12 * nm, h->stream);
+            for (int a = 0; a < 6; ++a) {
+                st[a] = p;
+                p += st_n[a];
+            }
+        }
+        // the outputs: the caller's, or one staged block
+        //   double loss[nm] | loss_hist[nm][epochs] | float dis[nm][ns] | int32 locs[nm][ns] | correct[nm]
+        float* dd = dis;
+        int32_t* ld = locs;
+        double* sl = loss;
+        int32_t* cd = correct;
+        double* hd = loss_hist;
+        if (!od) {
+            uint8_t* p = h->net_out.ensure<uint8_t>(8 * nm * (1 + ne) + 8 * nm * ns + 4 * nm, h->stream);
+            sl = reinterpret_cast<double*>(p);
+            hd = loss_hist ? sl + nm : nullptr;
+            dd = reinterpret_cast<float*>(p + 8 * nm * (1 + ne));
+            ld = reinterpret_cast<int32_t*>(dd + nm * ns);
+            cd = ld + nm * ns;
+        }
+        uint64_t* best = h->net_best.ensure<uint64_t>(2 * nm * ns, h->stream);
+        float* gd = h->net_g.ensure<float>(nm * ns, h->stream);
+        double* ws = h->net_ws.ensure<double>(5 * nm * ns, h->stream);
+        const NetModel* tab = shp_upload(h, h->net_tab, geo.tab);
+        if (!od)
+            for (int a = 0; a < 6; ++a)
+                OPOSE_HIP_CHECK(hipMemcpyAsync(st[a], host_st[a], st_n[a] * 4, hipMemcpyHostToDevice, h->stream));
+        OPOSE_HIP_CHECK(hipMemsetAsync(best, 0xff, 2 * nm * ns * 8, h->stream));
+        ProfEntry pe;
+        h->prof_begin(pe, "shapelet_net_train", 0, 0);
+        // Three launches per epoch, back to back in stream order: the forward pass into one key
+        // buffer, the head (which also resets the other buffer for the next epoch), the query step.
+        for (int e = 0; e < epochs; ++e) {
+            float step, bc2s;
+            net_adam_scalars(lr, step0 + e + 1, &step, &bc2s);
+            uint64_t* cur = best + (size_t)(e & 1) * nm * ns;
+            uint64_t* nxt = best + (size_t)((e + 1) & 1) * nm * ns;
+            launch_shapelet_net_forward(sd, offd, n_seq, D, t_pad, tab, n_models, geo.m_max, geo.tiles, st[0], cur,
+                                        h->stream);
+            launch_shapelet_net_head(cur, nxt, yd, n_seq, n_models, st[3], st[4], st[5], step, bc2s, true, gd, ws,
+                                     hd ? hd + e : nullptr, epochs, nullptr, nullptr, nullptr, nullptr, h->stream);
+            launch_shapelet_net_step(sd, offd, n_seq, D, tab, n_models, geo.m_max, cur, gd, st[0], st[1], st[2], step,
+                                     bc2s, nullptr, h->stream);
+        }
+        // the closing forward pass with the final parameters
+        uint64_t* cur = best + (size_t)(epochs & 1) * nm * ns;
+        launch_shapelet_net_forward(sd, offd, n_seq, D, t_pad, tab, n_models, geo.m_max, geo.tiles, st[0], cur, h->stream);
+        launch_shapelet_net_head(cur, nullptr, yd, n_seq, n_models, st[3], st[4], st[5], 0.0f, 1.0f, false, nullptr, ws,
+                                 sl, 1, dd, ld, cd, nullptr, h->stream);
+        h->prof_end(pe);
+        if (!od) {
+            for (int a = 0; a < 6; ++a)
+                OPOSE_HIP_CHECK(hipMemcpyAsync(host_st[a], st[a], st_n[a] * 4, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(loss, sl, 8 * nm, hipMemcpyDeviceToHost, h->stream));
+            if (loss_hist && ne)
+                OPOSE_HIP_CHECK(hipMemcpyAsync(loss_hist, hd, 8 * nm * ne, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(dis, dd, 4 * nm * ns, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(locs, ld, 4 * nm * ns, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipMemcpyAsync(correct, cd, 4 * nm, hipMemcpyDeviceToHost, h->stream));
+            OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        h->prof_drain();
+    });
+    return OPOSE_OK;
+}
+
+int opose_debug_shapelet_net_grad(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int t_pad,
+                                  const uint8_t* labels, const float* query, int m, const float* head, float* g,
+                                  float* dq, double* dhead, double* loss) {
+    if (!h || !seq || !off || !labels || !query || !head || !g || !dq || !dhead || !loss) return OPOSE_E_ARG;
+    const int64_t q_off[2] = {0, m};
+    NetGeom geo;
+    if (const int rc = net_check(h, off, n_seq, D, t_pad, labels, q_off, 1, &geo)) return rc;
+    OPOSE_TRY(h, {
+        enter_main(h);
+        const int64_t L = off[n_seq];
+        const size_t ns = (size_t)n_seq, nq = (size_t)m * D;
+        DevBuf sb, ob, yb, tb, qb, hb, bb, gb, wb, db, rb;
+        float* sd = sb.ensure<float>((size_t)std::max<int64_t>(L, 1) * D, h->stream);
+        int64_t* offd = ob.ensure<int64_t>(ns + 1, h->stream);
+        uint8_t* yd = yb.ensure<uint8_t>(ns, h->stream);
+        float* qd = qb.ensure<float>(nq, h->stream);
+        float* hd = hb.ensure<float>(4, h->stream);
+        uint64_t* best = bb.ensure<uint64_t>(ns, h->stream);
+        float* gd = gb.ensure<float>(ns, h->stream);
+        double* ws = wb.ensure<double>(5 * ns, h->stream);
+        float* dqd = db.ensure<float>(nq, h->stream);
+        double* rd = rb.ensure<double>(5, h->stream);  // dhead [4] | loss
+        const NetModel* tab = shp_upload(h, tb, geo.tab);
+        if (L) OPOSE_HIP_CHECK(hipMemcpyAsync(sd, seq, (size_t)L * D * 4, hipMemcpyHostToDevice, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(offd, off, (ns + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(yd, labels, ns, hipMemcpyHostToDevice, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(qd, query, nq * 4, hipMemcpyHostToDevice, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(hd, head, 16, hipMemcpyHostToDevice, h->stream));
+        OPOSE_HIP_CHECK(hipMemsetAsync(best, 0xff, ns * 8, h->stream));
+        launch_shapelet_net_forward(sd, offd, n_seq, D, t_pad, tab, 1, m, geo.tiles, qd, best, h->stream);
+        launch_shapelet_net_head(best, nullptr, yd, n_seq, 1, hd, nullptr, nullptr, 0.0f, 1.0f, false, gd, ws, rd + 4, 1,
+                                 nullptr, nullptr, nullptr, rd, h->stream);
+        launch_shapelet_net_step(sd, offd, n_seq, D, tab, 1, m, best, gd, qd, nullptr, nullptr, 0.0f, 1.0f, dqd,
+                                 h->stream);
+        OPOSE_HIP_CHECK(hipMemcpyAsync(g, gd, ns * 4, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(dq, dqd, nq * 4, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(dhead, rd, 32, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipMemcpyAsync(loss, rd + 4, 8, hipMemcpyDeviceToHost, h->stream));
+        OPOSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->prof_drain();
+    });
+    return OPOSE_OK;
 }

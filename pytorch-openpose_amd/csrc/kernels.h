@@ -215,6 +215,25 @@ void launch_shapelet_scan_pick(const float* dist, const uint64_t* mask, const in
 void launch_shapelet_scan_offsets(const int32_t* counts, int n, bool first, int64_t* running, int64_t* occ_off,
                                   hipStream_t st);
 
+// shapelet_net.hip: the learned shapelet model (opose_shapelet_net_train).  models [n_models] and the
+// concatenated queries / moments they index; best [n_models][n_seq] keys (bits of s) << 32 | c, all
+// ones before a forward launch; tiles: ceil(most positions of any clip and model / kNetTC)
+size_t shapelet_net_q_bytes(int m, int D);
+size_t shapelet_net_x_bytes(int m, int D);
+void launch_shapelet_net_forward(const float* seq, const int64_t* off, int n_seq, int D, int t_pad,
+                                 const NetModel* models, int n_models, int m_max, int tiles, const float* query,
+                                 uint64_t* best, hipStream_t st);
+// g [n_models][n_seq], ws [n_models][5][n_seq]; next, g, loss_out, dis / locs / correct and dhead may
+// be null (shapelet_net.hip says what each is)
+void launch_shapelet_net_head(const uint64_t* best, uint64_t* next, const uint8_t* labels, int n_seq, int n_models,
+                              float* head, float* head_m, float* head_v, float step, float bc2s, bool update, float* g,
+                              double* ws, double* loss_out, int64_t loss_stride, float* dis, int32_t* locs,
+                              int32_t* correct, double* dhead, hipStream_t st);
+// the query's Adam step in place, or with dq_out the gradient alone
+void launch_shapelet_net_step(const float* seq, const int64_t* off, int n_seq, int D, const NetModel* models,
+                              int n_models, int m_max, const uint64_t* best, const float* g, float* query, float* q_m,
+                              float* q_v, float step, float bc2s, float* dq_out, hipStream_t st);
+
 // post.hip
 void launch_gauss_nms(const void* avg, bool f32, int NP, int H, int W, double thre, int cap, int* cnt, int* list,
                       double* list_score, hipStream_t st);

@@ -42,6 +42,19 @@ constexpr int kScanPickPairs = 4;
 // opose_shapelet_scan: patterns per chunk when the caller passes max_pats = 0 (the distance
 // workspace is that many rows of L floats: 256 MB at L = 10^6)
 constexpr int kScanDefaultPats = 64;
+// opose_shapelet_net_train: models trained side by side in one call (grid z of the forward kernel)
+constexpr int kNetMaxModels = 16;
+// shapelet_net_forward: a workgroup of kNetTC threads takes kNetTC consecutive positions of one clip
+// against one model's query, e over d in steps of kNetDU columns and a remainder.  The query goes
+// to LDS when its m * D floats fit kNetQLdsBytes, the clip's tile of kNetTC + m - 1 rows when it
+// fits kNetXLdsBytes (both together stay below the 64 KB a launch gets without an attribute call);
+// what does not fit is read from global memory.
+constexpr int kNetTC = 64;
+constexpr int kNetDU = 4;
+constexpr int kNetQLdsBytes = 16384;
+constexpr int kNetXLdsBytes = 40960;
+// shapelet_net_head (one workgroup per model) and shapelet_net_step (a thread per query element)
+constexpr int kNetThreads = 256;
 
 // kShpTR consecutive candidate starts r0 .. r0 + nvalid - 1 of sequence `seq`; out0: the row of the
 // launch's output that start r0 writes
@@ -68,6 +81,13 @@ struct ScanPat {
     int32_t m, slot;
     float sigma;
     int32_t pad;
+};
+
+// shapelet_net_*: one model of a training call.  row0: the first row of its query in the
+// concatenated queries (and of its moments); m: the rows of its query
+struct NetModel {
+    int64_t row0;
+    int32_t m, pad;
 };
 
 }  // namespace opose

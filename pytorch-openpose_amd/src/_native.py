@@ -118,6 +118,9 @@ SIGNATURES = {
     "opose_debug_shapelet_score": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
     "opose_shapelet_scan": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _I]),
     "opose_debug_shapelet_pick": (_I, [_P, _P, _P, _I, _I, C.c_float, _P, _P, _P, _L]),
+    "opose_shapelet_net_train": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _I, _D, _P, _P, _P,
+                                      _P, _P, _I]),
+    "opose_debug_shapelet_net_grad": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 EXPORTED = list(SIGNATURES)
 

@@ -1,7 +1,9 @@
 """Shapelet search over motion data on the device: the reference's srcmx/PreprocessingData.py
 MotionJointFeatures, srcmx/utilmx.py SlidingDistance and srcmx/shapeletmodel.py
 ShapeletMatrixModel.train through libopose's shapelet entry points (include/opose.h states the
-distance, score and selection rules; tests/shapelet_cases.py restates them in NumPy).
+distance, score and selection rules; tests/shapelet_cases.py restates them in NumPy), and the learned
+model, srcmx/shapeletmodel.py ShapeletNetModel with the records of srcmx/shapeletlearning.py
+FindShaplets_Net_ED, through opose_shapelet_net_train (tests/shapelet_net_cases.py).
 
 Host arrays in give host arrays out.  torch CUDA tensors in give CUDA tensors out, ordered on
 torch's current stream (Handle.torch_call), with no host round trip of the data; the row offsets and
@@ -262,6 +264,183 @@ def shapelet_scan(patterns, sigmas, seq, off, cap=None, max_pats=0, handle=None)
         pos, dist = call(room)
     n = min(total, room)
     return {"off": occ_off, "pos": pos[:n], "dist": dist[:n]}
+
+
+NET_STATE = ("query", "head", "q_m", "q_v", "head_m", "head_v")
+
+
+def shapelet_net_train(seq, off, labels, queries, heads, state=None, step0=0, epochs=0, lr=0.01, t_pad=0,
+                       loss_hist=False, handle=None):
+    """opose_shapelet_net_train on a ragged batch seq [L, D] / off: n_models models, one per query
+    of `queries` (a list of [m_k, D]) and row of heads [n_models, 4] = (w0, w1, b0, b1), take
+    `epochs` Adam steps side by side (include/opose.h states the rule; 0 epochs: the forward pass
+    alone).  state: the dict a previous call returned, to continue it (its queries, heads, moments
+    and step count then replace queries / heads / step0).  Nothing passed in is modified.
+
+    Returns a dict: "query" (the concatenated queries [sum m_k, D]), "queries" (its per-model
+    views), "head", "q_m", "q_v", "head_m", "head_v", "step", "q_off", and from the closing forward
+    pass "dis" float32 / "locs" int32 [n_models, n_seq], "loss" float64 / "correct" int32
+    [n_models]; "loss_hist" float64 [n_models, epochs] when asked for.  Host arrays in give host
+    arrays out; a CUDA seq gives CUDA tensors, ordered on torch's current stream."""
+    import torch
+    dev = _is_dev(seq)
+    off = np.ascontiguousarray(off, np.int64)
+    lab = _labels(labels)
+    n_seq = len(off) - 1
+    if len(lab) != n_seq:
+        raise ValueError("one label per clip")
+
+    def own(a):  # a private float32 copy on the side of seq
+        if dev:
+            return torch.as_tensor(a, device=seq.device).to(torch.float32).contiguous().clone()
+        return np.array(a.cpu() if hasattr(a, "cpu") else a, np.float32, order="C")
+
+    if state is not None:
+        st = {k: own(state[k]) for k in NET_STATE}
+        q_off, step0 = np.ascontiguousarray(state["q_off"], np.int64), int(state["step"])
+    else:
+        qs = [own(q) for q in queries]
+        q_off = _offsets([len(q) for q in qs])
+        st = {"query": (torch.cat(qs, dim=0).contiguous() if dev else np.ascontiguousarray(np.concatenate(qs)))
+              if len(qs) else own(np.zeros((0, 1)))}
+        st["head"] = own(heads).reshape(-1, 4)
+        for k, like in (("q_m", "query"), ("q_v", "query"), ("head_m", "head"), ("head_v", "head")):
+            st[k] = torch.zeros_like(st[like]) if dev else np.zeros_like(st[like])
+    n_models = len(q_off) - 1
+    if dev:
+        seq = seq.to(torch.float32).contiguous()
+    else:
+        seq = np.ascontiguousarray(seq, np.float32)
+    D = seq.shape[1]
+    if seq.shape[0] == 0:  # every clip empty (padded mode): a pointer to pass, no row of it is a clip's
+        seq = torch.zeros((1, D), dtype=torch.float32, device=seq.device) if dev else np.zeros((1, D), np.float32)
+    if st["query"].ndim != 2 or st["query"].shape[1] != D or len(st["query"]) != q_off[-1]:
+        raise ValueError("queries and clips differ in their feature columns")
+    if tuple(st["head"].shape) != (n_models, 4):
+        raise ValueError("one head (w0, w1, b0, b1) per query")
+    h = handle or default_handle(seq.device.index if dev else 0)
+    epochs = int(epochs)
+    dis, locs = _empty(dev, seq, (n_models, n_seq), np.float32), _empty(dev, seq, (n_models, n_seq), np.int32)
+    loss, correct = _empty(dev, seq, n_models, np.float64), _empty(dev, seq, n_models, np.int32)
+    hist = _empty(dev, seq, (n_models, max(epochs, 0)), np.float64) if loss_hist else None
+    _run(h, dev, lib.opose_shapelet_net_train, _native._ptr(seq), off.ctypes.data, n_seq, D, int(t_pad),
+         lab.ctypes.data, q_off.ctypes.data, n_models, *[_native._ptr(st[k]) for k in NET_STATE], int(step0), epochs,
+         float(lr), _native._ptr(dis), _native._ptr(locs), _native._ptr(loss), _native._ptr(correct),
+         _native._ptr(hist) if loss_hist else None, _native.DEVICE_IO if dev else 0)
+    st.update({"queries": [st["query"][a:b] for a, b in zip(q_off[:-1], q_off[1:])], "q_off": q_off,
+               "step": int(step0) + epochs, "dis": dis, "locs": locs, "loss": loss, "correct": correct})
+    if loss_hist:
+        st["loss_hist"] = hist
+    return st
+
+
+def _net_batch(X):
+    """The clips of a ShapeletNetModel call -> (seq, off, t_pad, dev): an [N, D, T] batch is N clips
+    of T rows (its padding is part of the data, as in the reference); a list of [T_i, D] clips is
+    padded to the longest by the library's t_pad."""
+    seq, off, dev = _ragged(X)
+    t_pad = int(np.max(np.diff(off))) if isinstance(X, (list, tuple)) else 0
+    return seq, off, t_pad, dev
+
+
+class ShapeletNetModel:
+    """The reference's learned shapelet model (srcmx/shapeletmodel.py:11-90) on libopose: a query
+    [1, D, m] and a Linear(1, 2) head on the smallest squared sliding distance of each clip, trained
+    by Adam on the cross-entropy.  X is an [N, D, T] array or tensor padded as in the reference, or
+    a list of [T_i, D] clips (padded to the longest without materialising it); Y the N labels."""
+
+    def __init__(self, shape, query=None, lr=0.01, handle=None):
+        import torch
+        m, d = shape
+        if query is None:
+            query = torch.randn(1, d, m, dtype=torch.float32)
+        query = torch.as_tensor(query).detach().cpu().to(torch.float32)
+        if tuple(query.shape) != (1, d, m):
+            raise ValueError("query must be shaped [1, D, m]")
+        cls = torch.nn.Linear(1, 2)  # on the CPU: a seeded run starts where the reference's does
+        w, b = cls.weight.detach().numpy(), cls.bias.detach().numpy()
+        self.shape, self.lr, self.handle = (int(m), int(d)), float(lr), handle
+        self.state = {"query": np.ascontiguousarray(query[0].numpy().T), "q_off": np.array([0, m], np.int64),
+                      "head": np.array([[w[0, 0], w[1, 0], b[0], b[1]]], np.float32), "step": 0}
+        for k, like in (("q_m", "query"), ("q_v", "query"), ("head_m", "head"), ("head_v", "head")):
+            self.state[k] = np.zeros_like(self.state[like])
+        self.loss_hist = None
+
+    @property
+    def query(self):
+        """float32 [1, D, m], as the reference's parameter."""
+        return np.ascontiguousarray(self.state["query"].T[None])
+
+    @property
+    def head(self):
+        return self.state["head"][0]
+
+    def _call(self, X, Y, epochs, loss_hist=False):
+        seq, off, t_pad, dev = _net_batch(X)
+        if Y is None:
+            Y = np.zeros(len(off) - 1, np.uint8)
+        res = shapelet_net_train(seq, off, Y, None, None, state=self.state, epochs=epochs, lr=self.lr, t_pad=t_pad,
+                                 loss_hist=loss_hist, handle=self.handle)
+        return {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in res.items() if k != "queries"}
+
+    def train(self, X, Y, epochs=10000):
+        """`epochs` Adam steps, all enqueued at once; loss_hist keeps each epoch's loss."""
+        res = self._call(X, Y, epochs, loss_hist=True)
+        self.state = {k: res[k] for k in NET_STATE + ("q_off", "step")}
+        self.loss_hist = res["loss_hist"][0]
+        return self
+
+    def __call__(self, X, Y):
+        """(DIS float32 [N], loc int32 [N], score) of the current parameters."""
+        res = self._call(X, Y, 0)
+        return res["dis"][0], res["locs"][0], int(res["correct"][0]) / res["dis"].shape[1]
+
+    def localizeshape(self, X):
+        res = self._call(X, None, 0)
+        return res["locs"][0], res["dis"][0]
+
+    def getshapelet(self):
+        """The learned window, float32 [m, D]."""
+        return self.state["query"].copy()
+
+
+def net_records(samples, labels, m_lens=range(15, 40, 2), init=None, epochs=10000, lr=0.01, handle=None):
+    """The arrays FindShaplets_Net_ED (srcmx/shapeletlearning.py:223-310) writes per window length,
+    for every length of m_lens from one training call and without the h5 file: {m: {"locs": int16
+    [positives], "dists": float32 [positives], "shapelet": float32 [1, D, m], "score": float32 [1]}}.
+    samples: a list of [T_i, D] clips, padded to the longest as the reference pads them.  Each
+    length's query starts at a window of a clip: init maps a length to (clip, start), e.g. a
+    brute-force model's (shapeindex, cand); a length it does not name takes the reference's
+    fallback, clip 0 at start 127, and ValueError when that window does not fit the padded clip.
+    Every head is a CPU nn.Linear(1, 2), drawn in the order of m_lens."""
+    import torch
+    lab = np.asarray(labels.cpu() if hasattr(labels, "cpu") else labels) != 0
+    m_lens = [int(m) for m in m_lens]
+    seq, off, t_pad, dev = _net_batch(list(samples))
+    host = seq.cpu().numpy() if dev else seq
+    queries, heads = [], []
+    for m in m_lens:
+        clip, start = (init or {}).get(m, (0, 127))
+        clip, start = int(clip), int(start)
+        if not 0 <= clip < len(off) - 1 or start < 0 or start + m > t_pad:
+            raise ValueError("the starting window of length %d (clip %d, start %d) does not fit" % (m, clip, start))
+        q = np.zeros((m, host.shape[1]), np.float32)  # rows past the clip's end are the padding
+        rows = host[off[clip] + start:max(min(off[clip] + start + m, off[clip + 1]), off[clip] + start)]
+        q[:len(rows)] = rows
+        queries.append(q)
+        cls = torch.nn.Linear(1, 2)
+        w, b = cls.weight.detach().numpy(), cls.bias.detach().numpy()
+        heads.append([w[0, 0], w[1, 0], b[0], b[1]])
+    res = shapelet_net_train(seq, off, lab, queries, np.array(heads, np.float32), epochs=epochs, lr=lr, t_pad=t_pad,
+                             handle=handle)
+    def host(v):
+        return v.cpu().numpy() if hasattr(v, "cpu") else v
+
+    res = {k: [host(q) for q in v] if k == "queries" else host(v) for k, v in res.items()}
+    return {m: {"locs": res["locs"][k][lab].astype(np.int16), "dists": res["dis"][k][lab].astype(np.float32),
+                "shapelet": np.ascontiguousarray(res["queries"][k].T[None]).astype(np.float32),
+                "score": np.array([int(res["correct"][k]) / len(lab)]).astype(np.float32)}
+            for k, m in enumerate(m_lens)}
 
 
 class ShapeletMatrixModel:
