@@ -38,6 +38,10 @@
  *   AugmentateOneShapelet          .py:78-153                opose_debug_shapelet_pick (the hit walk)
  *   ShapeletNetModel (train,       srcmx/shapeletmodel.py:   opose_shapelet_net_train;
  *   __call__, localizeshape)       11-90                     opose_debug_shapelet_net_grad (one backward)
+ *   GCN_muti_att (eval forward)    cls/TGCN/tgcn_model.py:   opose_tgcn_create + opose_tgcn_forward;
+ *                                  93-129                    opose_debug_tgcn_layer (one layer)
+ *   test()'s four-copy mean        cls/TGCN/test_tgcn.py:    opose_tgcn_forward (copies)
+ *                                  31-39
  *
  * Conventions: plain pointers and sizes only; 0 = OK, negative = error (see opose_status).
  * Host pointers are caller-owned and read-only; the library copies them. A handle owns one
@@ -829,6 +833,64 @@ int opose_debug_shapelet_pick(opose_t* h, const float* dist, const int64_t* off,
 int opose_debug_shapelet_net_grad(opose_t* h, const float* seq, const int64_t* off, int n_seq, int D, int t_pad,
                                   const uint8_t* labels, const float* query, int m, const float* head, float* g,
                                   float* dq, double* dhead, double* loss);
+
+/* ---- TGCN sign classifier (cls/TGCN/tgcn_model.py GCN_muti_att, evaluation mode) -------------
+ * Inference only: Dropout is the identity and every BatchNorm1d(V * H) uses its running statistics,
+ * as cls/TGCN/test_tgcn.py runs the model.
+ *
+ * Shapes: V nodes (the reference hard-codes 55), F_in input and H hidden features, C classes,
+ * n_stage >= 0 residual blocks, is_resi.  1 + 2 n_stage graph-convolution layers: the stem F_in -> H,
+ * then two H -> H layers per block.
+ *
+ * params: one float32 blob, n_params values.  Per layer, stem first, then each block's gc1 / bn1 and
+ * gc2 / bn2:
+ *     W [F][H] | att [V][V] | bias [H] | gamma [V H] | beta [V H] | running_mean [V H] | running_var [V H]
+ * (F = F_in for the stem, H after it; the batch-norm arrays in the reference's view(b, -1) order,
+ * element v H + f), then fc_out.weight [C][H] | fc_out.bias [C].
+ *
+ * Rule, for a sample x [V][F_in]:
+ *   layer(x)[v][f] = tanhf( (sum over u of att[v][u] * (sum over k of x[u][k] W[k][f])) * a[v][f] + c[v][f] )
+ *   with a = gamma / sqrt(running_var + bn_eps), c = beta + (bias - running_mean) * a, both formed
+ *   in float64 at create time and rounded to float32 once;
+ *   y = layer_stem(x); per block: y = layer_2(layer_1(y)) (+ y when is_resi);
+ *   logits[c] = (sum over f of fc_w[c][f] * m[f]) + fc_b[c],  m[f] = (sum over v of y[v][f]) / V.
+ * Order of every sum the kernels fix: both matrix products run on the bf16 matrix cores with each
+ * fp32 operand as three exact bf16 pieces p0 + p1 + p2 and the six piece products (0,2) (0,0) (0,1)
+ * (1,0) (2,0) (1,1) (A piece, B piece; A = x, then att).  x W: k in chunks of 32 ascending, per chunk
+ * the six products in that order, one matrix instruction each, all into one fp32 accumulator from
+ * +0.  att (x W): x W split again, then the nodes u in two steps 0..31 and 32..63 (att reads as 0 at
+ * and past V), six products each, one accumulator from +0.  Then one multiply by a, one add of c
+ * (no fused multiply-add), tanhf, one add of the residual.  Head: m[f] over v ascending from +0,
+ * then one division; logits over f ascending from +0 (multiply, then add), then + fc_b[c]; all fp32.
+ * The result is fp32-class, not bit-equal to a float64 evaluation (tests/tgcn_cases.py holds the
+ * bound); bit for bit, a sample's result does not depend on the other samples of its call, on
+ * max_samples, or on the run.
+ *
+ * opose_tgcn_create checks, in this order, before anything is allocated: null pointers, V, F_in, H,
+ * C < 1 or n_stage < 0 (OPOSE_E_ARG); V > 64, F_in or H > 1024, C > 4096, n_stage > 64
+ * (OPOSE_E_SHAPE); bn_eps <= 0, n_params not the count above, a running_var + bn_eps that is not
+ * positive (OPOSE_E_ARG).  Several models may live on one handle; a model is used with the handle
+ * that made it and destroyed before it (opose_tgcn_destroy waits for the handle's stream). */
+typedef struct opose_tgcn opose_tgcn_t;
+int opose_tgcn_create(opose_t* h, int V, int F_in, int H, int C, int n_stage, int is_resi, double bn_eps,
+                      const float* params, int64_t n_params, opose_tgcn_t** model);
+int opose_tgcn_destroy(opose_t* h, opose_tgcn_t* model);
+/* x [B][V][copies F_in] float32: copy i of batch element b is columns [i F_in, (i + 1) F_in), read in
+ * place (cls/TGCN/test_tgcn.py:31-39).  The B copies samples (sample = b copies + i) run in chunks
+ * of max_samples (0: as many as keep an activation buffer within 64 MB), 1 + 2 n_stage + 1 launches
+ * per chunk on the handle's stream.  copy_logits [B][copies][C] (or NULL) receives every copy's
+ * logits, logits [B][C] = (sum over i ascending of copy_logits[b][i][c], fp32 from +0) / copies.
+ * flags: OPOSE_IN_DEVICE / OPOSE_OUT_DEVICE as for the shapelet entry points (host outputs: the
+ * call returns when they are written; device outputs: asynchronous on the handle's stream).
+ * Checked before any launch: null pointers, B < 1, copies < 1, max_samples < 0 (OPOSE_E_ARG);
+ * copies B >= 2^24 (OPOSE_E_SHAPE). */
+int opose_tgcn_forward(opose_t* h, const opose_tgcn_t* model, const float* x, int B, int copies, int max_samples,
+                       float* logits, float* copy_logits, int flags);
+/* One graph-convolution layer alone on host arrays, synchronously: layer 0 is the stem, 1 + 2 s and
+ * 2 + 2 s the two layers of block s.  x_in [B][V][F] (F the layer's input features), residual
+ * [B][V][H] or NULL (added after tanhf whatever is_resi says), out [B][V][H]. */
+int opose_debug_tgcn_layer(opose_t* h, const opose_tgcn_t* model, int layer, const float* x_in, int B,
+                           const float* residual, float* out);
 
 #ifdef __cplusplus
 }

@@ -441,6 +441,9 @@ struct opose_ctx {
     // opose_shapelet_net_train: the model table, the two (distance, location) key buffers, g, the
     // head's per-clip terms, and the staged state and outputs of a call on host memory
     opose::DevBuf net_tab, net_best, net_g, net_ws, net_state, net_out;
+    // opose_tgcn_forward: the staged input, a chunk's three activation buffers (a block's input,
+    // middle and output), and the logits and per-copy logits the caller did not give device room for
+    opose::DevBuf tg_x, tg_act[3], tg_out;
     // opose_batch_hand_extract cuts its 2N crops into chunks the conv kernels can address (as
     // opose_hand_infer_crops does); OPOSE_EXTRACT_CHUNK=n at handle creation: n crops per chunk
     // instead (tests/test_gpu_hand_extract.py runs a small batch in two chunks)

@@ -234,6 +234,33 @@ void launch_shapelet_net_step(const float* seq, const int64_t* off, int n_seq, i
                               int n_models, int m_max, const uint64_t* best, const float* g, float* query, float* q_m,
                               float* q_v, float step, float bc2s, float* dq_out, hipStream_t st);
 
+// tgcn.hip: the TGCN sign classifier (opose_tgcn_forward).  A graph-convolution layer is one launch
+// of tgcn_gc: workgroup (column tile of kTgcnTN, group of kTgcnG samples), 4 waves, wave w owning
+// rows 16 w .. 16 w + 15 of the kTgcnV padded nodes.
+constexpr int kTgcnV = 64, kTgcnG = 4, kTgcnTN = 64, kTgcnThreads = 256;
+constexpr int kTgcnMaxF = 1024, kTgcnMaxC = 4096, kTgcnMaxStage = 64;
+// units (16 bytes, 8 bf16) of a layer's packed W [H tiles][F chunks of 32][3 pieces][4 k-groups][64
+// columns] and of its packed att [2 k-steps][3 pieces][4 k-groups][64 rows]
+inline size_t tgcn_w_units(int F, int H) {
+    return (size_t)((H + kTgcnTN - 1) / kTgcnTN) * ((F + 31) / 32) * 3 * 4 * kTgcnTN;
+}
+constexpr size_t kTgcnAttUnits = 2 * 3 * 4 * kTgcnV;
+struct TgcnLayer {
+    const uint8_t* w;    // packed W
+    const uint8_t* att;  // packed att
+    const float* a;      // [V][H] folded batch-norm scale
+    const float* c;      // [V][H] folded batch-norm shift (the layer's bias included)
+    int F, H;
+};
+// x: sample n of the launch is rows of ld floats at x + ((n_in0 + n) / copies) V ld + ((n_in0 + n) %
+// copies) F; res (or null) and out: [n][V][H] dense
+void launch_tgcn_gc(const TgcnLayer& L, int V, const float* x, int64_t ld, int copies, int64_t n_in0, int n,
+                    const float* res, float* out, hipStream_t st);
+// y [n1 - n0][V][H]: the last layer's output of the global samples n0 .. n1 - 1 (sample = b copies +
+// i); copy_logits [B copies][C] and logits [B][C] are indexed globally
+void launch_tgcn_head(const float* y, int64_t n0, int64_t n1, int copies, int V, int H, int C, const float* fcT,
+                      const float* fcb, float* copy_logits, float* logits, hipStream_t st);
+
 // post.hip
 void launch_gauss_nms(const void* avg, bool f32, int NP, int H, int W, double thre, int cap, int* cnt, int* list,
                       double* list_score, hipStream_t st);

@@ -121,6 +121,10 @@ SIGNATURES = {
     "opose_shapelet_net_train": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _I, _D, _P, _P, _P,
                                       _P, _P, _I]),
     "opose_debug_shapelet_net_grad": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "opose_tgcn_create": (_I, [_P, _I, _I, _I, _I, _I, _I, _D, _P, _L, C.POINTER(_P)]),
+    "opose_tgcn_destroy": (_I, [_P, _P]),
+    "opose_tgcn_forward": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I]),
+    "opose_debug_tgcn_layer": (_I, [_P, _P, _I, _P, _I, _P, _P]),
 }
 EXPORTED = list(SIGNATURES)
 
